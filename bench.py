@@ -16,9 +16,16 @@ process touches the GPU).  The config-3 side figure `train_ddp` is the one
 leg with a real exchange: TrainLoop.run_step at 128^3 bf16, batch 1 per GPU,
 the bucketed gradient all-reduce over RCCL overlapped with the backward.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-`roofline` for the dominant kernel (conv3d implicit GEMM, all launches of a
-step) and `cpu_baseline` (the CPU oracle timed on this host, rank 0, N=1).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run
+does only what the headline figure needs: set-up, warm-up, the timed steps,
+`--dump-outputs`, the line.  `--full` adds every side figure: `roofline` for
+the dominant kernel (conv3d implicit GEMM, all launches of one extra eager
+step), the other precisions, batch sizes, configurations and training legs,
+and `cpu_baseline` (the CPU oracle timed on this host, rank 0, N=1).
+
+`--dump-outputs DIR` writes what the last timed step handed its caller
+(rank 0's `sample`, float32) to DIR/sample.npy; inputs and noise are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -164,6 +171,24 @@ def launch_ranks(n):
         procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=env))
     rcs = [p.wait() for p in procs]
     return max(rcs, key=abs)
+
+
+DUMP_MAX_BYTES = 32 << 20   # per array; a larger one is cut to a fixed seeded sample of its elements
+
+
+def dump_outputs(outdir, arrays):
+    """Write each tensor of `arrays` as outdir/<name>.npy in float32: whole
+    when it fits DUMP_MAX_BYTES, else the elements (of the flattened NCDHW
+    array) at a fixed, seeded, sorted set of positions."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, ten in arrays.items():
+        a = ten.detach().float().cpu().contiguous().numpy()
+        keep = DUMP_MAX_BYTES // 4
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def time_loop(loop, n, world, sync):
@@ -371,9 +396,19 @@ def main():
                                                             "config 5: fp16)")
     ap.add_argument("--fp16", type=int, default=5, help="also time K config-2 steps with the U-Net in fp16 "
                                                         "(0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every side figure (roofline step, batched, respaced, fp32/fp32x/fp16, "
+                         "wavunet, config 5, training legs, CPU baseline); without it only the headline loop "
+                         "runs and the per-leg options above are ignored")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (rank 0) to DIR/<name>.npy")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: exercise the rank launch / barrier / max-over-ranks plumbing only")
     args = ap.parse_args()
+    if not args.full:
+        for leg in ("cpu_baseline", "respaced", "batched", "fp32", "fp32x", "train", "wavunet", "config5", "train5",
+                    "fp16"):
+            setattr(args, leg, 0)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -443,25 +478,32 @@ def main():
         next(loop)
     sync()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        next(loop)
+        last = next(loop)
     sync()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     loop.close()
     ops.check_device_status("bench timed loop")   # (after the timed region: it synchronises)
+    if args.dump_outputs and rank == 0 and last is not None:
+        # the loop's static buffers: nothing has run since the last timed step
+        dump_outputs(args.dump_outputs, {k: v for k, v in last.items() if v is not None})
+    del last
 
     # roofline of the dominant kernel -- the implicit-GEMM MFMA conv kernels:
     # hipEvents around each of their launches over one extra (eager) step, on
     # the stream they run on; GroupNorm pre-passes, split-K finishes and the
     # sampler are HBM-bound kernels outside this figure
     plan = model.plan
-    plan.set_profiling(True)
-    loop = diffusion._native_loop(model, x_T, [T - 1], cond, True, graph=False)
-    next(loop)
-    torch.cuda.synchronize()
-    conv_ms, conv_flops, n_conv = plan.profile_read()
-    plan.set_profiling(False)
-    loop.close()
+    conv_ms = None
+    if args.full:
+        plan.set_profiling(True)
+        loop = diffusion._native_loop(model, x_T, [T - 1], cond, True, graph=False)
+        next(loop)
+        torch.cuda.synchronize()
+        conv_ms, conv_flops, n_conv = plan.profile_read()
+        plan.set_profiling(False)
+        loop.close()
     step_flops = plan.flops(1, n, n, n)
 
     # serving side-figure: B volumes per batched step (the 16^3 / 8^3 levels of
@@ -593,7 +635,7 @@ def main():
     # HBM bytes of the same conv family per step, from the committed rocprofv3
     # PMC passes of this bench (tools/pmc_traffic.py; FETCH_SIZE x2 on gfx950)
     traffic, traffic_src = None, None
-    if n == 128 and args.dtype == "bf16":
+    if args.full and n == 128 and args.dtype == "bf16":
         for tj in TRAFFIC_JSONS:
             if os.path.exists(tj):
                 with open(tj) as fh:
@@ -604,7 +646,16 @@ def main():
     ms_per_step = 1000.0 * elapsed / args.steps
     value = world * args.steps / elapsed
     peak = F32_PEAK_TFLOPS if args.dtype == "fp32" else BF16_PEAK_TFLOPS   # fp16 MFMA: the bf16 rate
-    achieved = conv_flops / (conv_ms * 1e-3) / 1e12
+    roofline = None
+    if conv_ms is not None:
+        achieved = conv_flops / (conv_ms * 1e-3) / 1e12
+        roofline = {"bound": "mfma", "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
+                    "frac": round(achieved / peak, 4), "traffic": traffic,
+                    "traffic_unit": "HBM bytes per step of those launches (2 x FETCH_SIZE + WRITE_SIZE, "
+                                    f"{traffic_src})",
+                    "kernel": f"implicit-GEMM MFMA conv kernels (conv3d_v5 warp-specialised, conv3d_v4 DMA-staged, conv3d_sg "
+                              f"small-grid, brick, head2 output head: "
+                              f"{n_conv} launches per step, {conv_ms:.2f} ms, {conv_flops / 1e12:.2f} TFLOP)"}
     res = {
         "metric": "denoising-steps/sec on 8-ch 128^3 volumes (1000-step DDPM, i2i cWDM)",
         "value": round(value, 4),
@@ -635,13 +686,8 @@ def main():
         "train_config5_224": train5,
         "wavunet_128": wavunet,
         "mfma_util_whole_step": round(step_flops * (value / world) / 1e12 / peak, 4),
-        "roofline": {"bound": "mfma", "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
-                     "frac": round(achieved / peak, 4), "traffic": traffic,
-                     "traffic_unit": "HBM bytes per step of those launches (2 x FETCH_SIZE + WRITE_SIZE, "
-                                     f"{traffic_src})",
-                     "kernel": f"implicit-GEMM MFMA conv kernels (conv3d_v5 warp-specialised, conv3d_v4 DMA-staged, conv3d_sg "
-                               f"small-grid, brick, head2 output head: "
-                               f"{n_conv} launches per step, {conv_ms:.2f} ms, {conv_flops / 1e12:.2f} TFLOP)"},
+        "roofline": roofline,
+        "full": bool(args.full),
     }
     if cpu_state is not None:
         threads = cpu_threads()

@@ -11,7 +11,7 @@ for e in "$@"; do
 done
 for rep in 1 2; do
 for e in "$@"; do
-  env $e timeout -k 10 300 python -u bench.py --cpu-baseline 0 --respaced 0 --batched 0 --train 0 --fp32 0 --fp32x 0 --fp16 0 --wavunet 0 --train5 0 > $O/bench.json 2>&1
+  env $e timeout -k 10 300 python -u bench.py --full --cpu-baseline 0 --respaced 0 --batched 0 --train 0 --fp32 0 --fp32x 0 --fp16 0 --wavunet 0 --train5 0 > $O/bench.json 2>&1
   echo "$e :: $(tail -1 $O/bench.json | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["config5_224"]["ms_per_step"])')" | tee -a $O/bench_ab.txt
 done
 done

@@ -9,7 +9,8 @@ A=$R/abtree/$NAME
 SIDE="--cpu-baseline 0 --respaced 0 --batched 0 --train 0 --fp32 0 --fp32x 0 --fp16 0 --config5 0 --wavunet 0 --train5 0"
 run() {  # tree label rep
   cd $1
-  timeout -k 10 240 python -u bench.py --steps $STEPS --warmup 5 $SIDE > $O/$2_$3.json 2> $O/$2_$3.err
+  FULL=; grep -q -e '"--full"' bench.py && FULL=--full   # the roofline step: behind --full where the tree has it
+  timeout -k 10 240 python -u bench.py $FULL --steps $STEPS --warmup 5 $SIDE > $O/$2_$3.json 2> $O/$2_$3.err
   python3 -c "import json; d=json.loads(open('$O/$2_$3.json').read().strip().splitlines()[-1]); print('$2', $3, d['ms_per_step'], d['roofline']['frac'])"
 }
 for rep in $(seq 1 $REPS); do

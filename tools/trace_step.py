@@ -25,8 +25,9 @@ def main():
     # steps start at the time-embedding MLP (the first launch of every U-Net
     # forward; the sampler epilogue may live in the output head)
     marks = [i for i, r in enumerate(rows) if "time_embed_kernel" in r["Kernel_Name"]]
-    # the last step of the timed (graph-replayed) loop: bench.py ends with one
-    # eager profiling step whose setup copies would otherwise land in it
+    # --last: everything from the last time-embedding launch on -- a plain
+    # bench.py run ends with its last timed (graph-replayed) step, a --full
+    # run with side legs off ends with the eager roofline step
     if "--last" in sys.argv:
         step = rows[marks[-1]:]
     else:
