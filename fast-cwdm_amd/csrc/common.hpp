@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdlib>
 #include <string>
 
 #include "../../include/cwdm.h"
@@ -122,7 +123,38 @@ inline int dispatch_dtype(int dtype, F&& f) {
   return f(float{});
 }
 
+inline int ck_of(int dtype) { return 32 / dtype_size(dtype); }
+
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---- CWDM_* environment knobs (listed in DESIGN.md) ------------------------
+// The only readers of the environment in csrc.  A call site is a `static const`
+// local or a global's initialiser, so each knob is read once.
+// a number, or dflt when the variable is not set
+inline int env_int(const char* name, int dflt) {
+  const char* e = std::getenv(name);
+  return e ? std::atoi(e) : dflt;
+}
+inline long long env_ll(const char* name, long long dflt) {
+  const char* e = std::getenv(name);
+  return e ? std::atoll(e) : dflt;
+}
+inline double env_double(const char* name, double dflt) {
+  const char* e = std::getenv(name);
+  return e ? std::atof(e) : dflt;
+}
+// on unless the value starts with '0'
+inline bool env_not0(const char* name) {
+  const char* e = std::getenv(name);
+  return !(e && e[0] == '0');
+}
+// off unless the value starts with '1'
+inline bool env_is1(const char* name) {
+  const char* e = std::getenv(name);
+  return e && e[0] == '1';
+}
+// on if the variable is present, whatever its value
+inline bool env_set(const char* name) { return std::getenv(name) != nullptr; }
 
 // Division by a launch constant without the integer-division sequence: q =
 // (mulhi(n, m) + n) >> s with s = ceil(log2 d), m = floor(2^32 (2^s - d) / d) + 1
@@ -191,6 +223,4 @@ struct GnFinFuse {
   bool used;
 };
 extern thread_local GnFinFuse* g_gnfin;
-// run the offered finalize now if it is pending for d (d->a_gn == its ss)
-int gnfin_flush(const cwdm_conv3d_desc* d, hipStream_t s);
 }  // namespace cwdm

@@ -6,32 +6,16 @@
 #include <vector>
 
 #include "conv3d_kernels.hpp"
+#include "internal.hpp"
 
 namespace cwdm {
-extern template int launch_wide<bf16_t, 1>(const ConvParams&, hipStream_t);
-extern template int launch_conv<bf16_t, 32, 4, 2, 1>(const ConvParams&, hipStream_t);
-extern template int launch_conv<bf16_t, 16, 4, 4, 1>(const ConvParams&, hipStream_t);
-extern template int launch_conv<bf16_t, 8, 8, 4, 1>(const ConvParams&, hipStream_t);
-extern template int launch_wide<bf16_t, 2>(const ConvParams&, hipStream_t);
-extern template int launch_conv<bf16_t, 32, 4, 2, 2>(const ConvParams&, hipStream_t);
-extern template int launch_conv<bf16_t, 16, 4, 4, 2>(const ConvParams&, hipStream_t);
-extern template int launch_conv<bf16_t, 8, 8, 4, 2>(const ConvParams&, hipStream_t);
-extern template int launch_wide<f16_t, 1>(const ConvParams&, hipStream_t);
-extern template int launch_conv<f16_t, 32, 4, 2, 1>(const ConvParams&, hipStream_t);
-extern template int launch_conv<f16_t, 16, 4, 4, 1>(const ConvParams&, hipStream_t);
-extern template int launch_conv<f16_t, 8, 8, 4, 1>(const ConvParams&, hipStream_t);
-extern template int launch_wide<f16_t, 2>(const ConvParams&, hipStream_t);
-extern template int launch_conv<f16_t, 32, 4, 2, 2>(const ConvParams&, hipStream_t);
-extern template int launch_conv<f16_t, 16, 4, 4, 2>(const ConvParams&, hipStream_t);
-extern template int launch_conv<f16_t, 8, 8, 4, 2>(const ConvParams&, hipStream_t);
-extern template int launch_wide<float, 1>(const ConvParams&, hipStream_t);
-extern template int launch_conv<float, 32, 4, 2, 1>(const ConvParams&, hipStream_t);
-extern template int launch_conv<float, 16, 4, 4, 1>(const ConvParams&, hipStream_t);
-extern template int launch_conv<float, 8, 8, 4, 1>(const ConvParams&, hipStream_t);
-extern template int launch_wide<float, 2>(const ConvParams&, hipStream_t);
-extern template int launch_conv<float, 32, 4, 2, 2>(const ConvParams&, hipStream_t);
-extern template int launch_conv<float, 16, 4, 4, 2>(const ConvParams&, hipStream_t);
-extern template int launch_conv<float, 8, 8, 4, 2>(const ConvParams&, hipStream_t);
+CWDM_WIDE_INSTANCES(extern template, bf16_t)
+CWDM_SMALL_INSTANCES(extern template, bf16_t)
+CWDM_WIDE_INSTANCES(extern template, f16_t)
+CWDM_SMALL_INSTANCES(extern template, f16_t)
+CWDM_WIDE_INSTANCES(extern template, float)
+CWDM_SMALL_INSTANCES(extern template, float)
+
 // ---- weight packing: OIDHW fp32 -> [ct][chunk][tap][n][2 quads, swizzled] ----
 // stride-2 conv as a stride-1 conv over the space-to-depth input (stride2.hip):
 // expanded weight We[co][ph ci0 + ci][t] of w[co][ci][k] (ci0 original input channels)
@@ -234,15 +218,13 @@ int dispatch_brick(const ConvParams& p, const Brick& br, hipStream_t s) {
 // K-split factor: small grids (the U-Net's 32^3 .. 8^3 levels) get split-K so
 // that a launch has ~768 workgroups to spread over 256 CUs.
 inline int pick_ksplit(long long nblk, int total_chunks) {
-  static const long long target = [] { const char* e = std::getenv("CWDM_KSPLIT_TARGET"); return e ? std::atoll(e) : 768LL; }();
+  static const long long target = env_ll("CWDM_KSPLIT_TARGET", 768);
   if (nblk >= 512 || nblk >= target || total_chunks <= 1) return 1;
   int S = (int)((target + nblk - 1) / nblk);
   if (S > total_chunks) S = total_chunks;
   const int per = (total_chunks + S - 1) / S;
   return (total_chunks + per - 1) / per;
 }
-
-int ck_of(int dtype) { return 32 / dtype_size(dtype); }
 
 }  // namespace cwdm
 
@@ -261,9 +243,31 @@ extern "C" int64_t cwdm_conv3d_packed_bytes(int cout, int cin, int ksize, int dt
 }
 
 static int pack_impl(const float* w, int cout, int cin, int ksize, int dtype, void* packed, int transpose,
-                     cwdm_stream_t stream, int s2_ci0 = 0);
-namespace cwdm {
-extern thread_local std::vector<PackJob>* g_pack_batch;
+                     cwdm_stream_t stream, int s2_ci0 = 0) {
+  CWDM_REQUIRE(w && packed, CWDM_E_INVALID, "cwdm_conv3d_pack: null pointer");
+  CWDM_REQUIRE(ksize == 1 || ksize == 3, CWDM_E_UNSUPPORTED, "cwdm_conv3d_pack: kernel size must be 1 or 3");
+  CWDM_REQUIRE(dtype_compute(dtype), CWDM_E_INVALID, "cwdm_conv3d_pack: bad dtype");
+  const int ck = ck_of(dtype);
+  const int cin_real = cin;
+  if (transpose) cin = (int)ceil_div(cin, ck) * ck;
+  CWDM_REQUIRE(cin % ck == 0, CWDM_E_UNSUPPORTED,
+               "cwdm_conv3d_pack: input channels must be a multiple of " + std::to_string(ck));
+  const int NT = 32 * pick_nf(cout);
+  const int nct = (int)ceil_div(cout, NT);
+  const int ntaps = ksize * ksize * ksize;
+  const long long total = (long long)nct * (cin / ck) * ntaps * NT * ck;
+  if (g_pack_batch) {  // the U-Net plan collects its packs and launches them together (pack_batch_run)
+    g_pack_batch->push_back(PackJob{w, packed, total, cout, cin, ntaps, NT, transpose, cin_real, s2_ci0, 0, 0});
+    return CWDM_OK;
+  }
+  dim3 grid((unsigned)ceil_div(total, 256));
+  return dispatch_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(pack_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, w, cout, cin, ntaps, NT, nct,
+                       reinterpret_cast<T*>(packed), transpose, cin_real, s2_ci0);
+    CWDM_LAUNCHED();
+    return CWDM_OK;
+  });
 }
 
 extern "C" int cwdm_conv3d_pack(const float* w, int cout, int cin, int ksize, int dtype, void* packed,
@@ -303,34 +307,6 @@ extern "C" int cwdm_conv3d_pack_dgrad(const float* w, int cout, int cin, int ksi
   return pack_impl(w, cin, cout, ksize, dtype, packed, 1, stream);
 }
 
-static int pack_impl(const float* w, int cout, int cin, int ksize, int dtype, void* packed, int transpose,
-                     cwdm_stream_t stream, int s2_ci0) {
-  CWDM_REQUIRE(w && packed, CWDM_E_INVALID, "cwdm_conv3d_pack: null pointer");
-  CWDM_REQUIRE(ksize == 1 || ksize == 3, CWDM_E_UNSUPPORTED, "cwdm_conv3d_pack: kernel size must be 1 or 3");
-  CWDM_REQUIRE(dtype_compute(dtype), CWDM_E_INVALID, "cwdm_conv3d_pack: bad dtype");
-  const int ck = ck_of(dtype);
-  const int cin_real = cin;
-  if (transpose) cin = (int)ceil_div(cin, ck) * ck;
-  CWDM_REQUIRE(cin % ck == 0, CWDM_E_UNSUPPORTED,
-               "cwdm_conv3d_pack: input channels must be a multiple of " + std::to_string(ck));
-  const int NT = 32 * pick_nf(cout);
-  const int nct = (int)ceil_div(cout, NT);
-  const int ntaps = ksize * ksize * ksize;
-  const long long total = (long long)nct * (cin / ck) * ntaps * NT * ck;
-  if (g_pack_batch) {  // the U-Net plan collects its packs and launches them together (pack_batch_run)
-    g_pack_batch->push_back(PackJob{w, packed, total, cout, cin, ntaps, NT, transpose, cin_real, s2_ci0, 0, 0});
-    return CWDM_OK;
-  }
-  dim3 grid((unsigned)ceil_div(total, 256));
-  return dispatch_dtype(dtype, [&](auto tag) -> int {
-    using T = decltype(tag);
-    hipLaunchKernelGGL(pack_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, w, cout, cin, ntaps, NT, nct,
-                       reinterpret_cast<T*>(packed), transpose, cin_real, s2_ci0);
-    CWDM_LAUNCHED();
-    return CWDM_OK;
-  });
-}
-
 namespace cwdm {
 thread_local std::vector<PackJob>* g_pack_batch = nullptr;
 
@@ -340,7 +316,7 @@ int pack_batch_run(std::vector<PackJob>& jobs, int dtype, PackJob* table, std::v
                    hipStream_t s) {
   if (jobs.empty()) return CWDM_OK;
   // the tiled kernel's jobs (no stride-2 fold, ntaps <= 27) first, then the gather kernel's
-  static const bool tiled_on = [] { const char* e = std::getenv("CWDM_PACK_TILED"); return !(e && e[0] == '0'); }();
+  static const bool tiled_on = env_not0("CWDM_PACK_TILED");
   auto tiled = [&](const PackJob& j) { return tiled_on && j.s2_ci0 == 0 && j.ntaps <= 27 && j.NT % 32 == 0; };
   std::stable_partition(jobs.begin(), jobs.end(), tiled);
   size_t nt = 0;
@@ -394,18 +370,6 @@ Plan1 plan_conv(const cwdm_conv3d_desc* d) {
   return q;
 }
 }  // namespace
-
-namespace cwdm {
-bool v4_eligible(const cwdm_conv3d_desc* d);
-bool v5_eligible(const cwdm_conv3d_desc* d, bool gn);
-int64_t v4_workspace_bytes(const cwdm_conv3d_desc* d);
-int conv3d_v4_forward(const cwdm_conv3d_desc* d, hipStream_t s);
-int legacy_conv3d_forward(const cwdm_conv3d_desc* d, cwdm_stream_t stream);
-bool head_eligible(const cwdm_conv3d_desc* d);
-int head_conv_forward(const cwdm_conv3d_desc* d, hipStream_t s);
-bool pw_eligible(const cwdm_conv3d_desc* d);
-int pw_forward(const cwdm_conv3d_desc* d, hipStream_t s);
-}  // namespace cwdm
 
 extern "C" int64_t cwdm_conv3d_workspace_bytes(const cwdm_conv3d_desc* d) {
   if (!d || d->B <= 0 || d->D <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0) return -1;

@@ -31,6 +31,7 @@
 #include <cstdlib>
 
 #include "conv3d_kernels.hpp"
+#include "internal.hpp"
 #include "sampler.hpp"
 
 namespace cwdm {
@@ -645,11 +646,16 @@ __global__ void __launch_bounds__(512) head2_kernel(HeadParams p, Head2Geo g) {
 }
 }  // namespace
 
-extern std::atomic<int> g_conv_path;
+// cwdm_debug_head2 (initial value: env CWDM_HEAD2=0 the first head, else the second)
+std::atomic<int> g_head2{env_not0("CWDM_HEAD2") ? 0 : -1};
 
 namespace {
-bool head2_ok(const cwdm_conv3d_desc* d);
+// the second-generation head where its shape holds
+bool head2_ok(const cwdm_conv3d_desc* d) {
+  return g_head2.load(std::memory_order_relaxed) >= 0 && d->a_c0 == 64 && d->W % 16 == 0 && d->H % 4 == 0 &&
+         d->D % 4 == 0;
 }
+}  // namespace
 
 bool head_eligible(const cwdm_conv3d_desc* d) {
   if (g_conv_path.load(std::memory_order_relaxed) == 1) return false;
@@ -658,17 +664,7 @@ bool head_eligible(const cwdm_conv3d_desc* d) {
          (d->W % 32 == 0 || head2_ok(d)) && d->H % 4 == 0 && d->D % 4 == 0 && d->D * d->H * d->W * d->a_c0 < (1LL << 31);
 }
 
-extern std::atomic<unsigned long long*> g_stamps;   // conv3d_v4.hip (cwdm_debug_conv_stamps)
-// cwdm_debug_head2 (initial value: env CWDM_HEAD2=0 the first head, else the second)
-std::atomic<int> g_head2{[] { const char* e = std::getenv("CWDM_HEAD2"); return (e && e[0] == '0') ? -1 : 0; }()};
-
 namespace {
-// the second-generation head where its shape holds
-bool head2_ok(const cwdm_conv3d_desc* d) {
-  return g_head2.load(std::memory_order_relaxed) >= 0 && d->a_c0 == 64 && d->W % 16 == 0 && d->H % 4 == 0 &&
-         d->D % 4 == 0;
-}
-
 Head2Geo head2_geo(const HeadParams& p, int& grid) {
   static const int ncu = [] {
     int dev = 0, n = 0;
@@ -733,7 +729,7 @@ int head_conv_forward(const cwdm_conv3d_desc* d, hipStream_t s) {
 
 bool head_sampler_eligible(const cwdm_conv3d_desc* d, const cwdm_sampler_args* a) {
   // CWDM_HEAD_SAMPLER=0: the unfused forward + cwdm_sampler_step (A/B switch)
-  static const bool on = [] { const char* e = std::getenv("CWDM_HEAD_SAMPLER"); return !(e && e[0] == '0'); }();
+  static const bool on = env_not0("CWDM_HEAD_SAMPLER");
   return on && head_eligible(d) && d->a_gn && d->cout == 8 && a->levels <= 1 && a->B == d->B && a->d == d->D && a->h == d->H &&
          a->w == d->W && a->x_t && a->x_prev && a->coef && a->t && a->T > 0 &&
          (!a->mirror || a->mirror_dtype == d->dtype || a->mirror_dtype == CWDM_F32);

@@ -1,10 +1,5 @@
 // Explicit instantiation: small-grid conv kernels, f32.
 #include "conv3d_kernels.hpp"
 namespace cwdm {
-template int launch_conv<float, 32, 4, 2, 1>(const ConvParams&, hipStream_t);
-template int launch_conv<float, 16, 4, 4, 1>(const ConvParams&, hipStream_t);
-template int launch_conv<float, 8, 8, 4, 1>(const ConvParams&, hipStream_t);
-template int launch_conv<float, 32, 4, 2, 2>(const ConvParams&, hipStream_t);
-template int launch_conv<float, 16, 4, 4, 2>(const ConvParams&, hipStream_t);
-template int launch_conv<float, 8, 8, 4, 2>(const ConvParams&, hipStream_t);
+CWDM_SMALL_INSTANCES(template, float)
 }  // namespace cwdm

@@ -1,6 +1,5 @@
 // Explicit instantiation: wide-grid conv kernels, bf16.
 #include "conv3d_kernels.hpp"
 namespace cwdm {
-template int launch_wide<bf16_t, 1>(const ConvParams&, hipStream_t);
-template int launch_wide<bf16_t, 2>(const ConvParams&, hipStream_t);
+CWDM_WIDE_INSTANCES(template, bf16_t)
 }  // namespace cwdm

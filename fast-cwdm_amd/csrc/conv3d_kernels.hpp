@@ -1085,4 +1085,18 @@ int launch_wide(const ConvParams& p, hipStream_t s) {
   return CWDM_OK;
 }
 
+// The explicit instances of launch_wide / launch_conv, listed once: conv3d.hip
+// declares them (KW = extern template) and the conv3d_inst_{wide,small}_<dtype>.hip
+// units, split for compile time, define them (KW = template).
+#define CWDM_WIDE_INSTANCES(KW, T)                                \
+  KW int launch_wide<T, 1>(const ConvParams&, hipStream_t);       \
+  KW int launch_wide<T, 2>(const ConvParams&, hipStream_t);
+#define CWDM_SMALL_INSTANCES(KW, T)                                     \
+  KW int launch_conv<T, 32, 4, 2, 1>(const ConvParams&, hipStream_t);   \
+  KW int launch_conv<T, 16, 4, 4, 1>(const ConvParams&, hipStream_t);   \
+  KW int launch_conv<T, 8, 8, 4, 1>(const ConvParams&, hipStream_t);    \
+  KW int launch_conv<T, 32, 4, 2, 2>(const ConvParams&, hipStream_t);   \
+  KW int launch_conv<T, 16, 4, 4, 2>(const ConvParams&, hipStream_t);   \
+  KW int launch_conv<T, 8, 8, 4, 2>(const ConvParams&, hipStream_t);
+
 }  // namespace cwdm

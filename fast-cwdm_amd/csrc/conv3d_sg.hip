@@ -449,7 +449,6 @@ template __global__ void conv3d_sg_kernel<f16_t, 8, 8, 0, 27>(SGParams);
 template __global__ void conv3d_sg_kernel<f16_t, 8, 8, 1, 27>(SGParams);
 template __global__ void conv3d_sg_kernel<f16_t, 8, 8, 0, 1>(SGParams);
 
-extern std::atomic<int> g_conv_path;
 // set by the U-Net plan around the accurate fast mode's K-expanded small-grid convs: a 16-bit conv
 // with fp32 output takes this kernel, its residual fp32 too (SgFp32xScope)
 thread_local bool g_sg_fp32x = false;
@@ -506,8 +505,8 @@ int sg_split_for(const cwdm_conv3d_desc* d, int cin, bool skip = false) {
   // level splits K 4 ways instead of 8, 66.28 -> 66.54 steps/s on one box,
   // config 5 unchanged -- profiles/r04/g_sg_target_ab.txt); the 1x1 skips' own
   // (env CWDM_SG_SKIP_TARGET, A/B knob, default the same)
-  static const int64_t target3 = [] { const char* e = std::getenv("CWDM_SG_TARGET"); return e ? std::atoll(e) : 192LL; }();
-  static const int64_t target1 = [] { const char* e = std::getenv("CWDM_SG_SKIP_TARGET"); return e ? std::atoll(e) : target3; }();
+  static const int64_t target3 = env_ll("CWDM_SG_TARGET", 192);
+  static const int64_t target1 = env_ll("CWDM_SG_SKIP_TARGET", target3);
   const int64_t target = skip ? target1 : target3;
   if (tiles >= target || nch < 2) return 1;
   int S = (int)std::min<int64_t>((target + tiles - 1) / tiles, nch);
@@ -569,15 +568,15 @@ void sg_go_t(const SGParams& q, const cwdm_conv3d_desc* d, int taps, hipStream_t
 }
 
 int sg_go(const SGParams& q0, const cwdm_conv3d_desc* d, int taps, double flops, hipStream_t s) {
-  static const int xcd_map = [] { const char* e = std::getenv("CWDM_SG_XCD"); return !(e && e[0] == '0'); }();
+  static const int xcd_map = env_not0("CWDM_SG_XCD");
   SGParams q = q0;
   q.xcd = xcd_map;
   // default 4: after the 4th of 9 groups (r06 same box: 16^3 convs 567 -> 523 us per step, 8^3 347 -> 332,
   // 15.36 -> 15.28 ms; conv_bench 16^3 -8 %, all-after-the-phase (9) -5 %)
-  static const int late = [] { const char* e = std::getenv("CWDM_SG_LATE"); return e ? std::atoi(e) : 4; }();
+  static const int late = env_int("CWDM_SG_LATE", 4);
   q.late = late < 0 ? 0 : (late > 9 ? 9 : late);
 #ifdef CWDM_SG_DIAG
-  static const int diag = [] { const char* e = std::getenv("CWDM_SG_DIAGMASK"); return e ? std::atoi(e) : 0; }();
+  static const int diag = env_int("CWDM_SG_DIAGMASK", 0);
   q.diag = diag;
 #endif
   prof_begin(s);

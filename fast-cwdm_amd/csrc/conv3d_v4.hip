@@ -198,30 +198,9 @@ int64_t src_voxels(const cwdm_conv3d_desc* d) {
 
 // kernel-path policy (cwdm_conv3d_set_path): 0 auto, 1 legacy only, 2 DMA kernels wherever the shape allows,
 // 3 as 2 without the warp-specialised kernel
-std::atomic<int> g_conv_path{[] {
-  const char* e = std::getenv("CWDM_CONV_PATH");
-  return e ? std::atoi(e) : 0;
-}()};
+std::atomic<int> g_conv_path{env_int("CWDM_CONV_PATH", 0)};
 
 std::atomic<unsigned long long*> g_stamps{nullptr};
-
-bool sg_eligible(const cwdm_conv3d_desc* d);
-bool sg_skip_eligible(const cwdm_conv3d_desc* d);
-int sg_launch(const V4Params& v, const cwdm_conv3d_desc* d, void* partial, hipStream_t s);
-int64_t ksplit_slice_voxels(const cwdm_conv3d_desc* d);
-bool pw_eligible(const cwdm_conv3d_desc* d);
-int pw_forward(const cwdm_conv3d_desc* d, hipStream_t s);
-bool pw_split_eligible(const cwdm_conv3d_desc* d);
-int pw_split_forward(const cwdm_conv3d_desc* d, hipStream_t s);
-int sg_ksplit(const cwdm_conv3d_desc* d);
-int sg_skip_launch(const cwdm_conv3d_desc* d, void* out, void* partial, hipStream_t s);
-int sg_skip_ksplit(const cwdm_conv3d_desc* d);
-int64_t sg_sync_bytes(int ksplit);
-bool v5_eligible(const cwdm_conv3d_desc* d, bool gn);
-int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
-              const float* agn, const void* res, int rmode, hipStream_t s, const V5Aa* aa = nullptr);
-int v5_aa_units(const cwdm_conv3d_desc* d, int* lead);
-unsigned* plan_aa_counters();
 
 int64_t v4_items(const cwdm_conv3d_desc* d) {
   return d->B * ((d->W + 31) / 32) * (d->H / 4) * (d->D / 4) * (d->cout / 64);
@@ -229,12 +208,9 @@ int64_t v4_items(const cwdm_conv3d_desc* d) {
 
 // work items a launch aims for before it splits K (env CWDM_V4_KSPLIT_TARGET)
 int64_t v4_ksplit_target() {
-  static const int64_t t = [] {
-    const char* e = std::getenv("CWDM_V4_KSPLIT_TARGET");
-    // 64 (r04; was 128): config 5's 28^3 64-channel down-block convs (49 tiles)
-    // then run unsplit on 32-channel tiles: 44 -> 19 us against the split legacy path
-    return e ? (int64_t)std::atoll(e) : (int64_t)64;
-  }();
+  // 64 (r04; was 128): config 5's 28^3 64-channel down-block convs (49 tiles)
+  // then run unsplit on 32-channel tiles: 44 -> 19 us against the split legacy path
+  static const int64_t t = env_ll("CWDM_V4_KSPLIT_TARGET", 64);
   return t;
 }
 
@@ -242,7 +218,7 @@ int64_t v4_ksplit_target() {
 // level): enough K slices for ~512 work items, at least two chunks per slice
 int v4_ksplit(const cwdm_conv3d_desc* d) {
   if (sg_eligible(d)) return sg_ksplit(d);  // the small-grid kernel's own K split (8^3 level)
-  const int ck = 32 / dtype_size(d->dtype);
+  const int ck = ck_of(d->dtype);
   const int nch = (d->a_c0 + d->a_c1) / ck;
   const int64_t nblk = v4_items(d);
   const int64_t target = v4_ksplit_target();
@@ -300,8 +276,6 @@ int64_t v4_workspace_bytes(const cwdm_conv3d_desc* d) {
   return ws;
 }
 
-int legacy_conv3d_forward(const cwdm_conv3d_desc* d, cwdm_stream_t stream);
-
 // the U-Net plan's backward: fuse the reduce pass of the SiLU(GroupNorm)
 // backward that follows this dgrad conv into its epilogue (GbwdFuse, conv3d_v4.hpp
 // V4Params::gx0); taken only by the 16-bit fast epilogue without K split
@@ -327,7 +301,7 @@ bool gn_fin_fusable(const GnFinFuse& f, int dtype, int c0, int c1) {
   // 32^3 -- with per-workgroup partials the 64^3 / 128^3 finalizes qualify too, but the fused pass
   // (~512 workgroups, each re-reducing its chunk's partials) streams the big grids far below the plain
   // pre-pass: r06 same box, 15.33 ms per step without the fusion there vs 15.52 (64^3) / 15.96 (128^3)
-  static const long long maxv = [] { const char* e = std::getenv("CWDM_GNFIN_MAXV"); return e ? std::atoll(e) : 32768LL; }();
+  static const long long maxv = env_ll("CWDM_GNFIN_MAXV", 32768);
   return cpg <= 16 && 16 % cpg == 0 && f.p0 <= 256 && (c1 == 0 || f.p1 <= 256) && f.voxels <= maxv;
 }
 
@@ -365,7 +339,7 @@ int gn_fin_apply(const GnFinFuse& f, const void* x0, int c0, const void* x1, int
 // 371 us of separate reduces (r06, profiles/r06/w_gbwd_maxw_ab.txt).  Env
 // CWDM_GBWD_MAXW, default 32.  Elsewhere the dgrad is an ordinary conv (v5 may take it).
 bool gbwd_grid_ok(const cwdm_conv3d_desc* d) {
-  static const int gb_maxw = [] { const char* e = std::getenv("CWDM_GBWD_MAXW"); return e ? std::atoi(e) : 32; }();
+  static const int gb_maxw = env_int("CWDM_GBWD_MAXW", 32);
   return g_gbwd && !g_gbwd->used && dtype_half(d->dtype) && d->W <= gb_maxw && d->a_mode == 0 && d->res_mode < 0 &&
          !d->stats;
 }
@@ -433,7 +407,7 @@ int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
   }
   // fewer 64-channel tiles than CUs (the 32^3 level): 32-channel tiles, one
   // z-plane per wave (twice the work items; the statistics bricks are the same)
-  static const bool ct32_on = [] { const char* e = std::getenv("CWDM_V4_CT32"); return !(e && e[0] == '0'); }();
+  static const bool ct32_on = env_not0("CWDM_V4_CT32");
   const bool ct32 = ct32_on && dtype_half(d->dtype) && S == 1 && !p.out_f32 && !p.accumulate && !p.out1 &&
                     (long long)p.B * p.tx * p.ty * p.tz * p.nct < 256 &&
                     (long long)p.D * p.H * p.W * p.cout * 2 < 0xFFFFE000LL;
@@ -448,12 +422,12 @@ int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
     return n > 0 ? n : 256;
   }();
   // workgroups per CU slot of the persistent grid (env CWDM_V4_GRID_MULT, A/B knob)
-  static const long long gmul = [] { const char* e = std::getenv("CWDM_V4_GRID_MULT"); return e ? std::atoll(e) : 4LL; }();
+  static const long long gmul = env_ll("CWDM_V4_GRID_MULT", 4);
   const dim3 grid((unsigned)std::min<long long>(nblk, gmul * ncu));
   // half a tile: ~17k cycles per chunk and ~12k for the epilogue when shared (tools/conv_stamps.py)
   // CWDM_CONV_STAGGER=-1 restores the half-tile delay; measured (r01 v7 kernel,
   // bench.py A/B on one MI355X): no delay 57.15 vs half-tile 56.80 steps/s
-  static const int stagger_env = [] { const char* e = std::getenv("CWDM_CONV_STAGGER"); return e ? std::atoi(e) : 0; }();
+  static const int stagger_env = env_int("CWDM_CONV_STAGGER", 0);
   p.stagger_cycles = nblk > 2LL * ncu ? (stagger_env >= 0 ? stagger_env : (p.nch * 17000 + 12000) / 2) : 0;
   // the fast epilogue addresses output / residual through 32-bit buffer offsets per batch
   const bool fast = !p.out_f32 && !p.accumulate && !p.out1 &&
@@ -745,7 +719,7 @@ int64_t apply_skip_lds_bytes(int dtype, int C, int cout, int64_t B) {
 }
 
 bool apply_skip_ok(int dtype, int C, int cout, int64_t B, int64_t vpb) {
-  const int ck = 32 / dtype_size(dtype);
+  const int ck = ck_of(dtype);
   const int qt = C * dtype_size(dtype) / 32;   // prefetch registers per thread (kernel's QT)
   return dtype_compute(dtype) && (cout == 64 || cout == 128) && vpb % 128 == 0 &&
          C % ck == 0 && qt <= 16 && apply_skip_lds_bytes(dtype, C, cout, B) <= 160 * 1024;
@@ -759,7 +733,7 @@ int gn_apply_skip(const void* x0, int c0, const void* x1, int c1, const float* g
   p.act = act; p.ws = reinterpret_cast<const unsigned char*>(wskip); p.cout = cout; p.skip = skip;
   const int64_t lds = apply_skip_lds_bytes(dtype, c0 + c1, cout, B);
   const int64_t nblocks = p.nvox / 128;
-  static const int64_t cap = [] { const char* e = std::getenv("CWDM_SKIP_GRID"); return e ? (int64_t)std::atoll(e) : (int64_t)512; }();
+  static const int64_t cap = env_ll("CWDM_SKIP_GRID", 512);
   const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(nblocks, cap)));
   auto go = [&](auto kern) -> int {
     CWDM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -35,6 +35,7 @@
 #include <type_traits>
 
 #include "conv3d_kernels.hpp"
+#include "internal.hpp"
 
 namespace cwdm {
 
@@ -102,6 +103,11 @@ __device__ unsigned g_v4_cu_arrivals[8 * 256];
 // scale / shift, the sweep lead and the per-chunk share of the kernel instance (v5_aa_units)
 constexpr int kV5AaWords = 4096;   // apply-ahead sweep counters of one launch (conv3d_v5.hip kV5AaCnt)
 struct V5Aa { const void* x0; int c0; const void* x1; int c1; const float* gn; int lead, units; unsigned* cnt; };
+
+// the launchers that take these (the rest of the cross-unit interface: internal.hpp)
+int sg_launch(const V4Params& v, const cwdm_conv3d_desc* d, void* partial, hipStream_t s);   // conv3d_sg.hip
+int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
+              const float* agn, const void* res, int rmode, hipStream_t s, const V5Aa* aa = nullptr);  // conv3d_v5.hip
 
 struct V4Cfg {
   static constexpr int HX = 34, HY = 6, HZ = 6, HV = HX * HY * HZ;  // 1224 halo voxels

@@ -1164,20 +1164,14 @@ __global__ void __launch_bounds__(512) conv3d_v5s_kernel(V4Params p) {
 
 namespace {
 int v5_mode() {
-  static const int m = [] { const char* e = std::getenv("CWDM_V5"); return e ? std::atoi(e) : 3; }();
+  static const int m = env_int("CWDM_V5", 3);
   return m;
 }
 }  // namespace
 
-bool sg_eligible(const cwdm_conv3d_desc* d);
-int v4_ksplit(const cwdm_conv3d_desc* d);
-extern std::atomic<int> g_conv_path;
-extern std::atomic<unsigned long long*> g_stamps;
 std::atomic<int> g_v5_grid{0};
-std::atomic<int> g_v5_aa{[] { const char* e = std::getenv("CWDM_V5_AA"); return e ? std::atoi(e) : 1; }()};
+std::atomic<int> g_v5_aa{env_int("CWDM_V5_AA", 1)};
 std::atomic<int> g_v5_aa_launches{0};
-int64_t v4_items(const cwdm_conv3d_desc* d);
-bool gbwd_grid_ok(const cwdm_conv3d_desc* d);
 std::atomic<int> g_v5_aa_extra{0};
 std::atomic<int> g_v5_aa_spin{0};
 // the U-Net plan asks for per-workgroup GroupNorm partials (V4Params::stats_wg) around its convs and
@@ -1262,7 +1256,7 @@ bool v5_eligible(const cwdm_conv3d_desc* d, bool gn) {
   // tiles per CU below which v4 (two workgroups per CU) keeps the conv (env
   // CWDM_V5_MIN_TPC, A/B knob; 1 since r04: config 5's 56^3 64-channel convs,
   // 392 tiles, 57 -> 53 us on v5)
-  static const double min_tpc = [] { const char* e = std::getenv("CWDM_V5_MIN_TPC"); return e ? std::atof(e) : 1.0; }();
+  static const double min_tpc = env_double("CWDM_V5_MIN_TPC", 1.0);
   return path == 2 || (double)v4_items(d) >= min_tpc * ncu;
 }
 
@@ -1279,7 +1273,7 @@ int v5_aa_units(const cwdm_conv3d_desc* d, int* lead) {
   // the helpers' share per chunk fits beside the drain from 8 input chunks (r05 stamps: the
   // 4-chunk 64-channel convs left them ~4k cycles behind the MFMA waves per chunk); env
   // CWDM_V5_AA_MINCH (A/B knob)
-  static const int minch = [] { const char* e = std::getenv("CWDM_V5_AA_MINCH"); return e ? std::atoi(e) : 8; }();
+  static const int minch = env_int("CWDM_V5_AA_MINCH", 8);
   if (mode == 1 && (d->a_c0 + d->a_c1) / 16 < minch) return 0;
   const int64_t V = d->D * d->H * d->W;
   if (V * C * 2 >= 0x7FFFF000LL) return 0;
@@ -1339,7 +1333,7 @@ int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
     p.agn = aa->gn;
     p.aa_lead = aa->lead;
     p.aa_units = aa->units;
-    static const int prio = [] { const char* e = std::getenv("CWDM_V5_AA_PRIO"); return e ? std::atoi(e) : 0; }();
+    static const int prio = env_int("CWDM_V5_AA_PRIO", 0);
     p.aa_prio = prio;
     CWDM_REQUIRE(aa->cnt, CWDM_E_INVALID, "conv3d_v5: apply-ahead counters missing");
     p.aa_cnt = aa->cnt;
@@ -1348,7 +1342,7 @@ int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
     p.aa_extra = g_v5_aa_extra.load(std::memory_order_relaxed);
   }
 #ifdef CWDM_V5_DIAG
-  static const int diag = [] { const char* e = std::getenv("CWDM_V5_DIAGMASK"); return e ? std::atoi(e) : 0; }();
+  static const int diag = env_int("CWDM_V5_DIAGMASK", 0);
   p.diag = diag;
 #endif
   p.stamps = g_stamps.load(std::memory_order_relaxed);

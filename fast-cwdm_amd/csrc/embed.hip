@@ -4,7 +4,7 @@
 // all blocks in one GEMV over the packed, concatenated weights.  The conv1 bias
 // of each block is folded into the projection bias, so conv1's epilogue adds a
 // single per-(b, c) vector.
-#include "common.hpp"
+#include "internal.hpp"
 
 namespace cwdm {
 namespace {

@@ -11,7 +11,7 @@
 #include <cmath>
 #include <type_traits>
 
-#include "common.hpp"
+#include "internal.hpp"
 
 namespace cwdm {
 namespace {
@@ -658,7 +658,7 @@ int dispatch_mode(int mode, F&& f) {
 // reduce at 2 M voxels: 132 us with 512 = 8 waves per CU, 114 us with 1024;
 // 2048 no better, profiles/r03/i_gnb_cap.txt)
 long long gn_bwd_blocks(int C, long long V) {
-  static const long long cap = [] { const char* e = std::getenv("CWDM_GNB_CAP"); return e ? std::atoll(e) : 1024LL; }();
+  static const long long cap = env_ll("CWDM_GNB_CAP", 1024);
   const long long slots = std::max(1, 256 / std::max(1, C / 8));
   long long nb = ceil_div(V, 4 * slots);
   if (nb > cap) nb = cap;
@@ -689,11 +689,6 @@ int launch_temb_bwd(const float* t, int B, int mc, const float* w1, const float*
   return CWDM_OK;
 }
 
-int gn_silu_bwd_impl(const void* x0, int c0, const void* x1, int c1, const void* du, int du_mode, const float* ss,
-                     const float* mr, const float* gamma, int groups, int64_t B, int64_t d, int64_t h, int64_t w,
-                     int dtype, void* dx0, int acc0, void* dx1, int acc1, float* dgamma, float* dbeta, void* ws,
-                     int64_t ws_bytes, float* chs, int64_t chs_stride, cwdm_stream_t stream, int acc_affine,
-                     const float* pre_part = nullptr, int pre_nblk = 0, const float** coef_out = nullptr);
 // Fixed-order slice sums of [B][nblk][W2] partial rows -> [B][slices][W2]
 // (the fused GroupNorm-backward partials: one row per dgrad tile, 4096 at
 // 128^3, too many for the single-workgroup gn_bwd_finalize).  Workgroup (slice,

@@ -17,6 +17,7 @@
 // at ~0.06 PF (690-910 us each, ~3 ms per training step).
 #include <atomic>
 #include "conv3d_kernels.hpp"
+#include "internal.hpp"
 
 namespace cwdm {
 
@@ -37,7 +38,7 @@ struct PwParams {
 
 thread_local GapplyFuse* g_gapply = nullptr;
 // the fused-apply skip dgrad's row-major epilogue on / off (cwdm_debug_pw_lt), and its launches
-std::atomic<int> g_pw_lt{[] { const char* e = std::getenv("CWDM_PW_LT"); return (e && e[0] == '0') ? 0 : 1; }()};
+std::atomic<int> g_pw_lt{env_not0("CWDM_PW_LT") ? 1 : 0};
 std::atomic<int> g_pw_lt_launches{0};
 
 namespace {
@@ -502,7 +503,6 @@ bool pw_eligible(const cwdm_conv3d_desc* d) {
   return d->B * d->D * d->H * d->W < (1LL << 40);
 }
 
-bool head_eligible(const cwdm_conv3d_desc* d);
 // the skip dgrad d runs pw_kernel and can take a GapplyFuse (the conditions pw_forward checks)
 bool pw_gapply_ok(const cwdm_conv3d_desc* d) {
   return !head_eligible(d) && pw_eligible(d) && d->cout % 8 == 0 && (!d->out1 || d->out_c0 % 8 == 0) &&
@@ -533,7 +533,7 @@ int pw_forward(const cwdm_conv3d_desc* d, hipStream_t s) {
   // the fused apply on 64-channel blocks where 128-channel ones would leave a
   // half-empty block (N = 192: 916 -> 770 us at 128^3; N = 128 stays on 128:
   // 491 vs 526 us); env CWDM_PW_GA_NM = 2 / 4 forces one (A/B knob)
-  static const int ga_nm = [] { const char* e = std::getenv("CWDM_PW_GA_NM"); return e ? std::atoi(e) : 0; }();
+  static const int ga_nm = env_int("CWDM_PW_GA_NM", 0);
   const int nm = !ga ? 4 : (ga_nm == 2 || ga_nm == 4) ? ga_nm : (d->cout % 128 ? 2 : 4);
   p.nnb = (int)ceil_div(d->cout, 32 * nm);
   const long long nblk = ceil_div(p.rows, 256) * p.nnb;

@@ -12,31 +12,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "common.hpp"
-
-namespace cwdm {
-int launch_time_embed(const float* t, int B, int mc, const float* w1, const float* b1, const float* w2,
-                      const float* b2, float* temb, hipStream_t s);
-int launch_emb_proj(const float* temb, int B, int E, const float* W, const float* bias, int R, float* out,
-                    hipStream_t s);
-int launch_vec_add(const float* a, const float* b, float* out, int64_t n, hipStream_t s);
-int launch_emb_bwd(const float* dEb, int R, int n, int B, const float* temb, int E, const float* W, float* dw,
-                   float* db, float* dcb, float* dsil, hipStream_t s, int acc);
-int launch_temb_bwd(const float* t, int B, int mc, const float* w1, const float* b1, const float* w2,
-                    const float* temb, const float* dsil, float* dw1, float* db1, float* dw2, float* db2,
-                    hipStream_t s);
-int gn_silu_bwd_impl(const void* x0, int c0, const void* x1, int c1, const void* du, int du_mode, const float* ss,
-                     const float* mr, const float* gamma, int groups, int64_t B, int64_t d, int64_t h, int64_t w,
-                     int dtype, void* dx0, int acc0, void* dx1, int acc1, float* dgamma, float* dbeta, void* ws,
-                     int64_t ws_bytes, float* chs, int64_t chs_stride, cwdm_stream_t stream, int acc_affine,
-                     const float* pre_part = nullptr, int pre_nblk = 0, const float** coef_out = nullptr);
-int gb_part_reduce(const float* part, int nblk, int C, int64_t B, int slices, float* out, hipStream_t s);
-bool pw_gapply_ok(const cwdm_conv3d_desc* d);
-int haar_nd_synth_add(int dtype, int64_t B, int64_t d, int64_t h, int64_t w, int C, const void* L, int64_t l_vs,
-                      float lll, const void* H, int64_t h_vs, float high, void* fine, int acc, hipStream_t s);
-int haar_nd_anal_add(int dtype, int64_t B, int64_t d, int64_t h, int64_t w, int C, const void* fine, void* L,
-                     int64_t l_vs, float lll, int accL, void* H, int64_t h_vs, float high, int accH, hipStream_t s);
-}  // namespace cwdm
+#include "internal.hpp"
 
 using namespace cwdm;
 
@@ -594,7 +570,7 @@ void build(cwdm_unet* u) {
   for (const auto& pr : u->params) { u->goff.push_back(go); go += pr.numel(); }
   u->grad_numel = go;
   // packed dgrad weights (every conv but conv_in, whose input needs no gradient)
-  const int ck = 32 / esize(c.dtype);
+  const int ck = ck_of(c.dtype);
   int64_t bo = 0;
   auto takeb = [&](int64_t bytes) { int64_t o = bo; bo = align_up(bo + bytes); return o; };
   for (size_t i = 0; i < u->convs.size(); ++i) {
@@ -605,64 +581,6 @@ void build(cwdm_unet* u) {
   }
   u->packed_bwd_bytes = bo;
 }
-
-}  // namespace
-namespace cwdm {
-bool v4_eligible(const cwdm_conv3d_desc* d);
-bool v5_eligible(const cwdm_conv3d_desc* d, bool gn);
-int head_split3_prep(const float* x, const float* gn, int64_t B, int64_t V, int C, void* x3, hipStream_t s);
-int head_split3_pack(const float* w, int cout, int cin, float* tmp, void* out, hipStream_t s, int k);
-int split3_prep(const float* x0, int c0, const float* x1, int c1, const float* gn, int64_t B, int64_t V, int cm,
-                void* x3, hipStream_t s);
-bool sg_skip_eligible(const cwdm_conv3d_desc* d);
-int sg_skip_ksplit(const cwdm_conv3d_desc* d);
-int sg_skip_launch(const cwdm_conv3d_desc* d, void* out, void* partial, hipStream_t s);
-bool sg_eligible(const cwdm_conv3d_desc* d);
-int sg_ksplit(const cwdm_conv3d_desc* d);
-int64_t ksplit_slice_voxels(const cwdm_conv3d_desc* d);
-extern thread_local bool g_sg_fp32x;
-bool pw_split_eligible(const cwdm_conv3d_desc* d);
-int pw_split_forward(const cwdm_conv3d_desc* d, hipStream_t s);
-bool apply_skip_ok(int dtype, int C, int cout, int64_t B, int64_t vpb);
-int gn_apply_skip(const void* x0, int c0, const void* x1, int c1, const float* gn, int64_t B, int64_t vpb, int dtype,
-                  const void* wskip, int cout, void* act, void* skip, hipStream_t s);
-int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
-              const void* res, int rmode, void* partial, hipStream_t s);
-extern thread_local unsigned* g_sg_sync;
-extern thread_local int g_stats_wg;         // conv3d_v5.hip: per-workgroup GroupNorm partials wanted
-extern thread_local int64_t g_stats_rows;   // ... and the rows the last launch wrote (0: per tile)
-int64_t sg_sync_bytes(int ksplit);
-int64_t plan_sync_bytes();
-bool head_eligible(const cwdm_conv3d_desc* d);
-extern thread_local std::vector<PackJob>* g_pack_batch;  // conv3d.hip
-int pack_batch_run(std::vector<PackJob>& jobs, int dtype, PackJob* table, std::vector<PackJob>& cache, hipStream_t s);
-// conv3d_v4.hip: where conv3d_v4_forward's GroupNorm pre-pass writes the
-// activated input (null: its own workspace), and whether it did
-extern thread_local void* g_act_keep;
-extern thread_local int g_act_kept;
-struct ActKeepScope {
-  void* ptr;
-  explicit ActKeepScope(void* p) : ptr(p) { g_act_keep = p; g_act_kept = 0; }
-  ~ActKeepScope() { g_act_keep = nullptr; }
-  bool used() const { return g_act_kept != 0; }
-};
-}  // namespace cwdm
-namespace {
-// the small-grid conv's K-split arrival counters for one launch list: one block
-// in the plan's workspace, zeroed once (a memset node) before the list -- each
-// K-split launch leaves its counters zero again -- and handed to the launches
-// for the duration of the call (conv3d_sg.hip)
-struct SgSyncScope {
-  SgSyncScope(void* block) { cwdm::g_sg_sync = reinterpret_cast<unsigned*>(block); }
-  ~SgSyncScope() { cwdm::g_sg_sync = nullptr; }
-};
-// the small-grid kernel's fp32 output / residual, for the K-expanded split convs only
-struct SgFp32xScope {
-  SgFp32xScope() { cwdm::g_sg_fp32x = true; }
-  ~SgFp32xScope() { cwdm::g_sg_fp32x = false; }
-};
-}  // namespace
-namespace {
 
 struct Layout {
   int64_t temb, ebias, split, split_bytes, sync;
@@ -794,8 +712,7 @@ Layout layout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) {
   // skip read x in one pass (cwdm::gn_apply_skip)
   L.skip_fused.assign(u->convs.size(), 0);
   int64_t skipb = 0;
-  const char* fe = std::getenv("CWDM_SKIP_FUSE");  // "0": A/B switch for the fused pass
-  const bool fuse = !(fe && fe[0] == '0');
+  const bool fuse = env_not0("CWDM_SKIP_FUSE");  // "0": A/B switch for the fused pass (read per plan)
   for (size_t i = 0; fuse && i < u->convs.size(); ++i) {
     const auto& c1 = u->convs[i];
     if (c1.skip_conv < 0 || c1.gn < 0 || c1.amode != 0) continue;
@@ -866,7 +783,7 @@ extern "C" int cwdm_unet_create(const cwdm_unet_config* cfg, cwdm_unet** plan) {
                CWDM_E_INVALID, "cwdm_unet_create: bad channel config");
   CWDM_REQUIRE(dtype_compute(cfg->dtype), CWDM_E_INVALID, "cwdm_unet_create: bad dtype");
   CWDM_REQUIRE(cfg->num_groups > 0, CWDM_E_INVALID, "cwdm_unet_create: bad num_groups");
-  const int ck = 32 / dtype_size(cfg->dtype);
+  const int ck = ck_of(cfg->dtype);
   CWDM_REQUIRE(cfg->in_channels % ck == 0, CWDM_E_UNSUPPORTED,
                "cwdm_unet_create: in_channels must be a multiple of " + std::to_string(ck));
   for (int l = 0; l < cfg->num_levels; ++l) {
@@ -1060,11 +977,6 @@ extern "C" double cwdm_unet_flops(const cwdm_unet* u, int64_t B, int64_t D, int6
   return f;
 }
 
-namespace cwdm {
-bool head_sampler_eligible(const cwdm_conv3d_desc* d, const cwdm_sampler_args* a);  // conv3d_head.hip
-int head_sampler_forward(const cwdm_conv3d_desc* d, const cwdm_sampler_args* a, hipStream_t s);
-}
-
 // samp: run the sampling step on the output (cwdm_unet_forward_step); fused
 // into the output head when it qualifies (*fused = 1), else after the forward.
 static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, const float* t, float* out,
@@ -1123,10 +1035,10 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
   // small grids the conv's pre-pass computes it; any other route runs it
   // first).  A pending one whose consumer is not the next step runs on its own.
   // Env CWDM_GNFIN=0: every finalize as its own launch (A/B switch).
-  static const bool fin_on = [] { const char* e = std::getenv("CWDM_GNFIN"); return !(e && e[0] == '0'); }();
+  static const bool fin_on = env_not0("CWDM_GNFIN");
   // statistics partial rows per tensor: the per-tile layout, or the rows of a warp-specialised conv
   // that summed them per workgroup (cwdm::g_stats_rows; env CWDM_STATS_WG=0: per tile everywhere)
-  static const int stats_wg = [] { const char* e = std::getenv("CWDM_STATS_WG"); return !(e && e[0] == '0'); }();
+  static const int stats_wg = env_not0("CWDM_STATS_WG");
   std::vector<int64_t> srows(L.s_parts);
   struct StatsWgScope {
     StatsWgScope() { cwdm::g_stats_wg = stats_wg; cwdm::g_stats_rows = 0; }
@@ -1420,7 +1332,7 @@ struct GLayout {
 constexpr int kGbSlices = 64;   // slice sums of the fused GroupNorm-backward partials (cwdm::gb_part_reduce)
 
 int ckpad(const cwdm_unet* u, int c) {
-  const int ck = 32 / esize(u->cfg.dtype);
+  const int ck = ck_of(u->cfg.dtype);
   return (c + ck - 1) / ck * ck;
 }
 
@@ -1655,7 +1567,7 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
   // pass of that backward when its kernel can (cwdm::GbwdFuse: 16-bit DMA conv,
   // no K split); pre then names the partials for gn_silu_bwd_impl
   struct Pre { const float* part = nullptr; int nblk = 0; };
-  static const bool gb_on = [] { const char* e = std::getenv("CWDM_GBWD_FUSE"); return !(e && e[0] == '0'); }();
+  static const bool gb_on = env_not0("CWDM_GBWD_FUSE");
   float* gbp = reinterpret_cast<float*>(gb + G.gbp);
   auto dgrad_gn = [&](int ci, const void* dy, int gi, int xid0, int xid1, Pre& pre) -> int {
     pre = Pre{};
@@ -1887,7 +1799,7 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
         CWDM_REQUIRE(!gf || gf->used, CWDM_E_UNSUPPORTED, "train plan: skip dgrad did not take the fused apply");
         return CWDM_OK;
       };
-      static const bool gapply_on = [] { const char* e = std::getenv("CWDM_GAPPLY_FUSE"); return !(e && e[0] == '0'); }();
+      static const bool gapply_on = env_not0("CWDM_GAPPLY_FUSE");
       const bool skip_gapply = c2.ws_p >= 0 && gapply_on && bk.updown == 0 && c2.sb0 == bk.x0 &&
                                c2.sb1 == bk.x1 && skip_dgrad(nullptr, true) == 1;
       if (c2.ws_p >= 0) {

@@ -2,7 +2,7 @@
 // thread).  Every product is rounded before the add (__fmul_rn/__fadd_rn), in
 // the stage order of the reference's matrices (DWT: H, W, D; IDWT: D, W, H),
 // so results match the oracle's elementwise restatement bit for bit.
-#include "common.hpp"
+#include "internal.hpp"
 #include "haar8.hpp"
 #include "sampler.hpp"
 
@@ -390,10 +390,6 @@ extern "C" int cwdm_sample_finish(const float* sample, int64_t B, int64_t d, int
                      sample, B, d, h, w, mask, keep_z, out);
   CWDM_LAUNCHED();
   return CWDM_OK;
-}
-
-namespace cwdm {
-int sampler2_launch(const cwdm_sampler_args* a, hipStream_t s);  // wavelet2.hip
 }
 
 extern "C" int cwdm_sampler_step(const cwdm_sampler_args* a, cwdm_stream_t stream) {

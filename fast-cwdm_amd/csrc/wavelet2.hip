@@ -9,7 +9,7 @@
 // synthesis and the sampler's process_xstart are all one-thread-per-block
 // register transforms (haar8.hpp, products rounded before adds like the
 // single-level kernels: bit-exact against the oracle).
-#include "common.hpp"
+#include "internal.hpp"
 #include <type_traits>
 
 #include "haar8.hpp"
@@ -429,7 +429,7 @@ int sampler2_launch(const cwdm_sampler_args* a, hipStream_t s) {
     vec |= 32;
   // the staged kernel: every tensor channels-last (channel stride 1), 16-byte
   // aligned rows, Philox noise (or none), no pred_xstart output
-  static const bool lds_on = [] { const char* e = std::getenv("CWDM_SAMPLER2_LDS"); return !(e && e[0] == '0'); }();
+  static const bool lds_on = env_not0("CWDM_SAMPLER2_LDS");
   const bool mir_ok = !a->mirror || ((vec & 32) && (a->mirror_dtype == CWDM_F32 ? ok(a->mirror, mi, 4) : true));
   // (or x_t / x_prev channel-planar: voxel stride 1, 4-byte aligned)
   const bool planar = xt.v == 1 && xp.v == 1 && a->x_t && a->x_prev;

@@ -8,7 +8,7 @@
 // GroupNorm that consumes it (same [B][parts][C][2] contract as the conv
 // epilogue).  One thread = one coarse voxel x 8 channels; a workgroup covers
 // 64 coarse voxels of one batch index (one statistics part).
-#include "common.hpp"
+#include "internal.hpp"
 #include "haar8.hpp"
 
 namespace cwdm {

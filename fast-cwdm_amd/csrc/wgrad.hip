@@ -1027,7 +1027,7 @@ bool hw_shape_ok(int cout, int cin, int ksize) { return ksize == 3 && cout >= 1 
 
 // the output head's weight gradient kernel where it applies (env CWDM_HEAD_WG=0: the brick kernel, A/B)
 bool hw_eligible(const cwdm_wgrad_desc* d) {
-  static const bool on = [] { const char* e = std::getenv("CWDM_HEAD_WG"); return !(e && e[0] == '0'); }();
+  static const bool on = env_not0("CWDM_HEAD_WG");
   if (!on || !hw_shape_ok(d->cout, d->u_c0 + d->u_c1, d->ksize) || !dtype_half(d->dtype)) return false;
   if (d->u_mode != 0 || d->u_cm || d->u1 || d->u_c1 != 0 || d->dy_cs < 8 || d->dy_cs % 8) return false;
   if (d->W % 16 || d->H % 4 || d->D % 4) return false;
@@ -1095,10 +1095,10 @@ extern "C" int cwdm_conv3d_wgrad(const cwdm_wgrad_desc* d, cwdm_stream_t stream)
   // cin <= cout (r05 A/B, profiles/r05/k_wgrad_ws_ab.txt: 64->64 477 -> 440 us, 64^3 128->128 219 ->
   // 205, the upsampling 128->128 1519 -> 1489; 192->64 / 128->64 / 384->128 1-4 % slower).  Env
   // CWDM_WG_WS=0: never, 2: every kept-activation call (A/B)
-  static const int ws_mode = [] { const char* e = std::getenv("CWDM_WG_WS"); return e ? std::atoi(e) : 1; }();
+  static const int ws_mode = env_int("CWDM_WG_WS", 1);
   const bool ws = d->u_cm && (ws_mode == 2 || (ws_mode == 1 && cin <= d->cout));
 #ifdef CWDM_WG_DIAG
-  static const bool force_mc1 = [] { const char* e = std::getenv("CWDM_WG_MC1"); return e && e[0] == '1'; }();
+  static const bool force_mc1 = env_is1("CWDM_WG_MC1");
   const int mc = (d->cout > 32 && !((force_mc1 || ws) && d->u_cm)) ? 2 : 1;
 #else
   const int mc = (d->cout > 32 && !ws) ? 2 : 1;
@@ -1118,7 +1118,7 @@ extern "C" int cwdm_conv3d_wgrad(const cwdm_wgrad_desc* d, cwdm_stream_t stream)
   const bool gn = d->u_gn != nullptr;
   const long long nw = (long long)d->cout * cin * p.taps;
   int rc;
-  static const bool wg1_on = !std::getenv("CWDM_WG1_OFF");   // A/B knob: the brick kernel for 1x1
+  static const bool wg1_on = !env_set("CWDM_WG1_OFF");   // A/B knob: the brick kernel for 1x1
   if (hw_eligible(d)) return d->dtype == CWDM_F16 ? launch_hw<f16_t>(d, s) : launch_hw<bf16_t>(d, s);
   if (wg1_on && wg1_eligible(d)) {
     // 1x1: the streaming kernel, accumulating straight into dw (no scratch)
@@ -1135,7 +1135,7 @@ extern "C" int cwdm_conv3d_wgrad(const cwdm_wgrad_desc* d, cwdm_stream_t stream)
     q.cin = cin; q.cout = d->cout; q.dy_cs = d->dy_cs;
     q.units = (int)(S * tiles); q.upx = (q.units + 7) / 8;
 #ifdef CWDM_WG_DIAG
-    static const int wg_diag = [] { const char* e = std::getenv("CWDM_WG_DIAGMASK"); return e ? std::atoi(e) : 0; }();
+    static const int wg_diag = env_int("CWDM_WG_DIAGMASK", 0);
     q.diag = wg_diag;
 #endif
     const long long sv = (long long)q.SD * q.SH * q.SW, V = d->D * d->H * d->W;

@@ -181,3 +181,13 @@ def test_wavunet_plan_refusals():
     # backward segments tile the parameters (head, each block incl. the pyramid convs, conv_in)
     tot = sum(plan.segment_range(s)[1] for s in range(plan.num_segments))
     assert tot == plan.grad_numel
+
+
+def test_environment_is_read_only_through_the_knob_helpers():
+    """Every CWDM_* knob of libcwdm goes through the env_* helpers of common.hpp
+    (one truth rule per helper; the knobs are listed in DESIGN.md): no other
+    file under csrc reads the environment itself."""
+    csrc = os.path.join(ROOT, "fast-cwdm_amd", "csrc")
+    users = sorted(f for f in os.listdir(csrc)
+                   if f.endswith((".hip", ".cpp", ".hpp", ".h")) and "getenv(" in open(os.path.join(csrc, f)).read())
+    assert users == ["common.hpp"], users
