@@ -179,7 +179,8 @@ struct PackJob {
   const float* w;
   void* out;
   long long total;
-  int cout, cin, ntaps, NT, transpose, cin_real, s2_ci0, pad;
+  int cout, cin, ntaps, NT, transpose, cin_real, s2_ci0;
+  int phase;   // the phase fold of an upsampling conv (cwdm_conv3d_pack_phase: ntaps 8, NT 64)
   long long blk0;
 };
 static_assert(sizeof(PackJob) == 64, "PackJob layout");

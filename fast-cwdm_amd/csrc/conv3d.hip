@@ -56,6 +56,49 @@ __device__ __forceinline__ void pack_elem(const float* __restrict__ w, int cout,
   out[i] = Elem<T>::from_f(v);
 }
 
+// element i of a phase-fold image [phase 8][ct][chunk][8 taps][64 n][2 quads, swizzled][EPQ]
+// (cwdm_conv3d_pack_phase): per axis, phase p tap t folds the original taps {0} / {1, 2} (p = 0) or
+// {0, 1} / {2} (p = 1); the fp32 sum runs kz, ky, kx ascending and is rounded once
+template <typename T>
+__device__ __forceinline__ void pack_phase_elem(const float* __restrict__ w, int cout, int cin, T* __restrict__ out,
+                                                long long i) {
+  constexpr int CK = ConvTr<T>::CK, EPQ = ConvTr<T>::EPQ;
+  const int nch = cin / CK, nct = cout / 64;
+  const int e = i % EPQ;
+  long long r = i / EPQ;
+  const int qp = r % 2;
+  r /= 2;
+  const int n = r % 64;
+  r /= 64;
+  const int tap = r % 8;
+  r /= 8;
+  const int chunk = r % nch;
+  r /= nch;
+  const int ct = r % nct;
+  const int ph = (int)(r / nct);
+  const int q = qp ^ ((n >> 3) & 1);
+  const int co = ct * 64 + n, ci = chunk * CK + q * EPQ + e;
+  // original taps [lo, hi] of (phase bit p, tap bit t)
+  auto lo = [](int p, int t) { return t == 0 ? 0 : 1 + p; };
+  auto hi = [](int p, int t) { return t == 0 ? p : 2; };
+  const int pz = ph >> 2, py = (ph >> 1) & 1, px = ph & 1, tz = tap >> 2, ty = (tap >> 1) & 1, tx = tap & 1;
+  const float* wc = w + ((long long)co * cin + ci) * 27;
+  float v = 0.f;
+  for (int kz = lo(pz, tz); kz <= hi(pz, tz); ++kz)
+    for (int ky = lo(py, ty); ky <= hi(py, ty); ++ky)
+      for (int kx = lo(px, tx); kx <= hi(px, tx); ++kx) v += wc[(kz * 3 + ky) * 3 + kx];
+  out[i] = Elem<T>::from_f(v);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) pack_phase_kernel(const float* __restrict__ w, int cout, int cin,
+                                                         T* __restrict__ out, long long total) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if constexpr (sizeof(T) == 2) {
+    if (i < total) pack_phase_elem<T>(w, cout, cin, out, i);
+  }
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ w, int cout, int cin, int ntaps, int NT,
                                                    int nct, T* __restrict__ out, int transpose, int cin_real,
@@ -82,9 +125,15 @@ __global__ void __launch_bounds__(256) pack_batch_kernel(const PackJob* __restri
 #pragma unroll
   for (int k = 0; k < 4; ++k) {  // 4 independent gathers in flight per thread
     const long long i = base + k * 256 + threadIdx.x;
-    if (i < j.total)
-      pack_elem<T>(j.w, j.cout, j.cin, j.ntaps, j.NT, reinterpret_cast<T*>(j.out), j.transpose, j.cin_real,
-                   j.s2_ci0, i);
+    if (i >= j.total) continue;
+    if constexpr (sizeof(T) == 2) {
+      if (j.phase) {
+        pack_phase_elem<T>(j.w, j.cout, j.cin, reinterpret_cast<T*>(j.out), i);
+        continue;
+      }
+    }
+    pack_elem<T>(j.w, j.cout, j.cin, j.ntaps, j.NT, reinterpret_cast<T*>(j.out), j.transpose, j.cin_real,
+                 j.s2_ci0, i);
   }
 }
 
@@ -292,6 +341,32 @@ extern "C" int cwdm_conv3d_pack_split(const float* w, int cout, int cin, void* p
   return CWDM_OK;
 }
 
+extern "C" int64_t cwdm_conv3d_packed_phase_bytes(int cout, int cin, int dtype) {
+  if (cout <= 0 || cout % 64 || cin <= 0 || cin % 16 || !dtype_half(dtype)) return -1;
+  return (int64_t)8 * (cout / 64) * (cin / 16) * 8 * 2048;
+}
+
+extern "C" int cwdm_conv3d_pack_phase(const float* w, int cout, int cin, int dtype, void* packed,
+                                      cwdm_stream_t stream) {
+  CWDM_REQUIRE(w && packed, CWDM_E_INVALID, "cwdm_conv3d_pack_phase: null pointer");
+  CWDM_REQUIRE(dtype_half(dtype) && cout > 0 && cout % 64 == 0 && cin > 0 && cin % 16 == 0, CWDM_E_UNSUPPORTED,
+               "cwdm_conv3d_pack_phase: bf16 / fp16, cout % 64 == 0, cin % 16 == 0");
+  const long long total = cwdm_conv3d_packed_phase_bytes(cout, cin, dtype) / 2;
+  if (g_pack_batch) {  // joins the U-Net plan's batched pack (pack_batch_run)
+    g_pack_batch->push_back(PackJob{w, packed, total, cout, cin, 8, 64, 0, cin, 0, 1, 0});
+    return CWDM_OK;
+  }
+  const dim3 grid((unsigned)ceil_div(total, 256));
+  if (dtype == CWDM_BF16)
+    hipLaunchKernelGGL(pack_phase_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, w, cout, cin,
+                       reinterpret_cast<bf16_t*>(packed), total);
+  else
+    hipLaunchKernelGGL(pack_phase_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, w, cout, cin,
+                       reinterpret_cast<f16_t*>(packed), total);
+  CWDM_LAUNCHED();
+  return CWDM_OK;
+}
+
 extern "C" int cwdm_conv3d_pack_s2(const float* w, int cout, int cin, int dtype, void* packed, int transpose,
                                    cwdm_stream_t stream) {
   // forward: a (cout -> 8 cin) conv over the space-to-depth input; transpose: its dgrad (8 cin outputs)
@@ -317,7 +392,9 @@ int pack_batch_run(std::vector<PackJob>& jobs, int dtype, PackJob* table, std::v
   if (jobs.empty()) return CWDM_OK;
   // the tiled kernel's jobs (no stride-2 fold, ntaps <= 27) first, then the gather kernel's
   static const bool tiled_on = env_not0("CWDM_PACK_TILED");
-  auto tiled = [&](const PackJob& j) { return tiled_on && j.s2_ci0 == 0 && j.ntaps <= 27 && j.NT % 32 == 0; };
+  auto tiled = [&](const PackJob& j) {
+    return tiled_on && j.s2_ci0 == 0 && !j.phase && j.ntaps <= 27 && j.NT % 32 == 0;
+  };
   std::stable_partition(jobs.begin(), jobs.end(), tiled);
   size_t nt = 0;
   while (nt < jobs.size() && tiled(jobs[nt])) ++nt;

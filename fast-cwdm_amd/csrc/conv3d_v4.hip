@@ -394,6 +394,8 @@ int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
   if (sg_eligible(d)) return sg_launch(p, d, partial, s);
   // the warp-specialised kernel (conv3d_v5.hip) where it applies (not the
   // backward's fused GroupNorm-reduce dgrad, not the stamps diagnostics build)
+  // an upsampling conv as eight phase convs on the source grid, where its phase weights came along
+  if (v5_phase_ok(d, rmode)) return v5_launch(d, a0, c0, a1, c1, a0_cm, nullptr, nullptr, -1, s, nullptr, true);
   if (v5_eligible(d, false))   // (refuses the dgrad that takes the fused GroupNorm-backward reduce)
     return v5_launch(d, a0, c0, a1, c1, a0_cm, nullptr, res, rmode, s);
   const int S = v4_ksplit(d);

@@ -39,6 +39,9 @@
 
 namespace cwdm {
 
+// (conv3d_v5 phase instance, MODE 2 -- a nearest-x2 upsampling conv as eight 2x2x2 phase convs: D, H, W
+// and the tiles are the SOURCE grid, the output grid is 2D x 2H x 2W, work item = (source tile, channel
+// tile, phase 4 pz + 2 py + px), aw = the phase pack of cwdm_conv3d_pack_phase)
 struct V4Params {
   int B, D, H, W;
   int tx, ty, tz;      // tiles per axis
@@ -107,7 +110,8 @@ struct V5Aa { const void* x0; int c0; const void* x1; int c1; const float* gn; i
 // the launchers that take these (the rest of the cross-unit interface: internal.hpp)
 int sg_launch(const V4Params& v, const cwdm_conv3d_desc* d, void* partial, hipStream_t s);   // conv3d_sg.hip
 int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
-              const float* agn, const void* res, int rmode, hipStream_t s, const V5Aa* aa = nullptr);  // conv3d_v5.hip
+              const float* agn, const void* res, int rmode, hipStream_t s, const V5Aa* aa = nullptr,
+              bool phase = false);  // conv3d_v5.hip
 
 struct V4Cfg {
   static constexpr int HX = 34, HY = 6, HZ = 6, HV = HX * HY * HZ;  // 1224 halo voxels
@@ -482,7 +486,7 @@ __device__ __forceinline__ void v4_epilogue(const V4Params& p, f32x16 (&acc)[2][
 // [c0, c1)) through the XCD-aware bijective map: the tiles an XCD runs are one
 // contiguous run (x fastest; K slice slowest, so the tiles an XCD runs share
 // their weight chunks).
-struct V4Tile { int b, sl, ct, x0, y0, z0, ks, c0, c1; };
+struct V4Tile { int b, sl, ct, x0, y0, z0, ks, c0, c1, ph; };   // ph: output phase (conv3d_v5 MODE 2), else 0
 __device__ __forceinline__ V4Tile v4_tile_of(const V4Params& p, int it) {
   const int tiles = p.tx * p.ty * p.tz;
   const int nbase = p.nblk / p.ksplit;
@@ -490,6 +494,7 @@ __device__ __forceinline__ V4Tile v4_tile_of(const V4Params& p, int it) {
   const int xcd = t & 7, q8 = p.nblk >> 3, r8 = p.nblk & 7;
   int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (t >> 3);
   V4Tile r;
+  r.ph = 0;
   r.ks = wg / nbase;
   wg -= r.ks * nbase;
   r.c0 = r.ks * p.kper;

@@ -36,6 +36,8 @@
 // The output is rounded to 16 bits before the residual add (v4 adds in fp32
 // and rounds once); without a residual the output is bit-identical to v4 on a
 // cwdm_gn_apply'd input.
+// MODE 2 is the phase instance for nearest-x2 upsampling convs (eight 2x2x2 convs
+// on the source grid, see above conv3d_v5_kernel).
 #include <atomic>
 #include <cstdlib>
 
@@ -143,7 +145,7 @@ __device__ __forceinline__ int v5aa_pos() {
 __device__ __forceinline__ V4Tile v5aa_tile_of(const V4Params& p, int it) {
   const int wg = it * (int)gridDim.x + v5aa_pos();
   V4Tile r;
-  r.ks = 0; r.c0 = 0; r.c1 = p.nch; r.b = 0;
+  r.ks = 0; r.c0 = 0; r.c1 = p.nch; r.b = 0; r.ph = 0;
   r.ct = wg % p.nct;
   r.sl = wg / p.nct;
   r.x0 = (r.sl % p.tx) * 32; r.y0 = ((r.sl / p.tx) % p.ty) * 4; r.z0 = (r.sl / (p.tx * p.ty)) * 4;
@@ -163,10 +165,59 @@ __host__ __device__ __forceinline__ unsigned v5aa_need(int j, int G, int nblk, i
   return (unsigned)(z1 < D ? z1 : D) * (unsigned)H * (unsigned)W;
 }
 
+// ---------------------------------------------------------------------------
+// Phase instance (MODE 2): a 3x3x3 conv over a nearest-x2 upsampled input as
+// eight 2x2x2 convs on the SOURCE grid.  Per axis, output index 2 i + p reads
+// the upsampled indices 2 i + p - 1 .. + 1 = source voxels {i - 1, i, i} (p = 0)
+// or {i, i, i + 1} (p = 1): a 2-tap conv over the source offsets p - 1 + t with
+// the weights [w0, w1 + w2] / [w0 + w1, w2] (cwdm_conv3d_pack_phase); the zero
+// padding agrees (upsampled -1 / 2 N is outside exactly when source -1 / N is).
+// Tiles, halo DMA and staging are those of a MODE 0 conv on the source grid
+// (V4Params D, H, W = the source grid); a work item is (source tile, channel
+// tile, phase), the 8 nct items of a source tile consecutive in v4_tile_of's
+// per-XCD run, so the items that read one halo run together on one XCD.  The
+// MFMA waves run 4 groups (tz, tx) x 2 planes per chunk, each step 2 ty taps x 4
+// lines = 8 MFMAs (64 per chunk instead of 216), on the halo shifted by the
+// phase; the helpers drain row (x, y, z) of the tile to output voxel
+// (2 x + px, 2 y + py, 2 z + pz).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ V4Tile v5p_tile_of(const V4Params& p, int it) {
+  const int tiles = p.tx * p.ty * p.tz;
+  const int t = blockIdx.x + it * gridDim.x;
+  const int xcd = t & 7, q8 = p.nblk >> 3, r8 = p.nblk & 7;
+  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (t >> 3);
+  V4Tile r;
+  r.ks = 0; r.c0 = 0; r.c1 = p.nch;
+  const int per = 8 * p.nct;
+  const int st = wg / per, in = wg - st * per;
+  r.ph = in / p.nct;
+  r.ct = in - r.ph * p.nct;
+  r.b = st / tiles;
+  r.sl = st - r.b * tiles;
+  r.x0 = (r.sl % p.tx) * 32; r.y0 = ((r.sl / p.tx) % p.ty) * 4; r.z0 = (r.sl / (p.tx * p.ty)) * 4;
+  r.ct = __builtin_amdgcn_readfirstlane(r.ct); r.b = __builtin_amdgcn_readfirstlane(r.b);
+  r.sl = __builtin_amdgcn_readfirstlane(r.sl); r.x0 = __builtin_amdgcn_readfirstlane(r.x0);
+  r.y0 = __builtin_amdgcn_readfirstlane(r.y0); r.z0 = __builtin_amdgcn_readfirstlane(r.z0);
+  r.ph = __builtin_amdgcn_readfirstlane(r.ph);
+  return r;
+}
+// the 5 source lines (y0 - 1 + py .. + 4) of plane K % 2 for group K / 2 = (tz, tx); hb carries the phase shift
+template <int K>
+__device__ __forceinline__ void v5p_read_step(u32x4 (&av)[6], const unsigned char* hb) {
+  constexpr int G = K / 2, PL = K % 2, TZ = G / 2, TX = G % 2;
+#pragma unroll
+  for (int L = 0; L < 5; ++L)
+    av[L] = *reinterpret_cast<const u32x4*>(hb + (((PL + TZ) * V4Cfg::HY + L) * V4Cfg::HX + TX) * 16);
+}
+#define V5P_WAIT_W(n, w) asm volatile("s_waitcnt vmcnt(" #n ")" : "+v"((w)[0]), "+v"((w)[1]) :: "memory")
+
 template <typename T, int MODE, bool GN, int AA = 0>
 __global__ void __launch_bounds__(512) conv3d_v5_kernel(V4Params p) {
   using C = V4Cfg;
   using T16 = T;
+  constexpr bool PH = MODE == 2;             // the phase instance
+  constexpr int HM = MODE == 1 ? 1 : 0;      // how the halo DMA reads the source
+  static_assert(!PH || (!GN && AA == 0), "the phase instance reads an activated or raw source");
   constexpr int NI = 10 + (GN ? 1 : 0);   // VMEM instructions per chunk of one helper wave
   __shared__ __attribute__((aligned(1024))) unsigned char smem[V5Cfg::SMEM];
 
@@ -175,7 +226,10 @@ __global__ void __launch_bounds__(512) conv3d_v5_kernel(V4Params p) {
   const int nblk = p.nblk;
   const int ntile = (nblk - (AA ? v5aa_pos() : (int)blockIdx.x) + (int)gridDim.x - 1) / (int)gridDim.x;
   if (ntile <= 0) return;
-  auto tile_of = [&](int it) { return AA ? v5aa_tile_of(p, it) : v4_tile_of(p, it); };
+  auto tile_of = [&](int it) {
+    if constexpr (PH) return v5p_tile_of(p, it);
+    else return AA ? v5aa_tile_of(p, it) : v4_tile_of(p, it);
+  };
   const int tiles = p.tx * p.ty * p.tz;
 
   // apply-ahead: this thread's lane slot among nslot cooperating lanes -- quad q (8 channels) of
@@ -274,12 +328,25 @@ __global__ void __launch_bounds__(512) conv3d_v5_kernel(V4Params p) {
       v4_gload(w[1], src + 3 * 2048);
       v4_gload(w[2], src + 6 * 2048);
     };
+    // phase instance: group g = (tz, tx) = taps 4 tz + tx (ty 0) and + 2 (ty 1) of the tile's phase
+    auto load_wp = [&](u32x4 (&w)[3], const V4Tile& t, int c, int g) {
+      if (V5_DIAG(4)) return;
+      const unsigned char* src = wlane + (((long long)t.ph * p.nct + t.ct) * p.nch + V5_PHYS(t, c)) * 8 * 2048 +
+                                 ((g >> 1) * 4 + (g & 1)) * 2048;
+      v4_gload(w[0], src);
+      v4_gload(w[1], src + 2 * 2048);
+    };
     const int hlane = hh * (C::HVP * 16) + (zb * (C::HX * C::HY) + lr) * 16;
     f32x16 acc[2][4];
-    u32x4 wr[3][3];
+    u32x4 wr[4][3];   // weight ring: slots 0-2 x 3 dy taps (phase instance: one slot per group, 2 ty taps each)
     V4Tile cur = tile_of(0);
-    load_w(wr[0], cur.ct, V5_PHYS(cur, cur.c0), 0);
-    load_w(wr[1], cur.ct, V5_PHYS(cur, cur.c0), 1);
+    if constexpr (PH) {
+      load_wp(wr[0], cur, cur.c0, 0);
+      load_wp(wr[1], cur, cur.c0, 1);
+    } else {
+      load_w(wr[0], cur.ct, V5_PHYS(cur, cur.c0), 0);
+      load_w(wr[1], cur.ct, V5_PHYS(cur, cur.c0), 1);
+    }
     __builtin_amdgcn_s_barrier();   // B0: chunk 0 transformed, bias 0 landed
     V5_STAMP(1, tid == 0);
     int gch = 0;
@@ -300,8 +367,34 @@ __global__ void __launch_bounds__(512) conv3d_v5_kernel(V4Params p) {
       }
       auto chunk = [&](auto lastc, int c) {
         constexpr bool LAST = decltype(lastc)::value;
-        const unsigned char* hb = smem + (gch % 3) * C::HALO_B + hlane;
         u32x4 av[2][6];
+        if constexpr (PH) {
+          // the halo shifted by the phase: plane + pz, line + py, column + px
+          const unsigned char* hb = smem + (gch % 3) * C::HALO_B + hlane +
+                                    ((((cur.ph >> 2) * C::HY + ((cur.ph >> 1) & 1)) * C::HX + (cur.ph & 1)) << 4);
+          if (!V5_DIAG(2)) v5p_read_step<0>(av[0], hb);
+          /* straight-line loads and counted waits, as below; weights two groups ahead: 2 loads per */
+          /* group, so the wait for group GI leaves the 4 loads of groups GI + 1, GI + 2 in flight  */
+#define V5P_STEP(K)                                                                                          \
+          {                                                                                                  \
+            constexpr int GI = (K) / 2, PL = (K) % 2, KN = (K) + 1, BC = (K) & 1;                            \
+            if (PL == 0) {                                                                                   \
+              if (GI + 2 < 4) load_wp(wr[(GI + 2) % 4], cur, c, GI + 2);                                     \
+              else if (!LAST) load_wp(wr[(GI + 2) % 4], cur, c + 1, GI - 2);                                 \
+              else load_wp(wr[(GI + 2) % 4], nxt, nxt.c0, GI - 2);                                           \
+            }                                                                                                \
+            if (KN < 8 && !V5_DIAG(2)) v5p_read_step<KN % 8>(av[BC ^ 1], hb);                                \
+            if (PL == 0) V5P_WAIT_W(4, wr[GI]);                                                              \
+            __builtin_amdgcn_sched_barrier(0);                                                               \
+            _Pragma("unroll") for (int ty = 0; ty < 2; ++ty)                                                 \
+            _Pragma("unroll") for (int m = 0; m < 4; ++m)                                                    \
+              v4_mfma<T>(acc[PL][m], wr[GI][ty], av[BC][m + ty]);                                            \
+            __builtin_amdgcn_sched_barrier(0);                                                               \
+          }
+          V5P_STEP(0) V5P_STEP(1) V5P_STEP(2) V5P_STEP(3) V5P_STEP(4) V5P_STEP(5) V5P_STEP(6) V5P_STEP(7)
+#undef V5P_STEP
+        } else {
+        const unsigned char* hb = smem + (gch % 3) * C::HALO_B + hlane;
         if (!V5_DIAG(2)) v4_read_step<0>(av[0], hb);
 #define V5_STEP(K)                                                                                           \
         {                                                                                                    \
@@ -327,6 +420,7 @@ __global__ void __launch_bounds__(512) conv3d_v5_kernel(V4Params p) {
         V5_STEP(6) V5_STEP(7) V5_STEP(8) V5_STEP(9) V5_STEP(10) V5_STEP(11)
         V5_STEP(12) V5_STEP(13) V5_STEP(14) V5_STEP(15) V5_STEP(16) V5_STEP(17)
 #undef V5_STEP
+        }
         V5_STAMP(2 + gch, tid == 0 && gch < 16);
         __builtin_amdgcn_s_barrier();   // chunk k read; chunk k + 1 transformed
         V5_STAMP(18 + gch, tid == 0 && gch < 16);
@@ -359,8 +453,13 @@ __global__ void __launch_bounds__(512) conv3d_v5_kernel(V4Params p) {
       __builtin_amdgcn_s_barrier();   // B2: tile staged
       cur = nxt;
     }
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(wr[0][0]), "+v"(wr[0][1]), "+v"(wr[0][2]), "+v"(wr[1][0]), "+v"(wr[1][1]),
-                 "+v"(wr[1][2])::"memory");   // the dummy reloads of the last tile
+    // the dummy reloads of the last tile
+    if constexpr (PH) {
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(wr[0][0]), "+v"(wr[0][1]), "+v"(wr[1][0]), "+v"(wr[1][1])::"memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(wr[0][0]), "+v"(wr[0][1]), "+v"(wr[0][2]), "+v"(wr[1][0]),
+                   "+v"(wr[1][1]), "+v"(wr[1][2])::"memory");
+    }
 #ifdef CWDM_CONV_STAMPS
     if (p.stamps && tid == 0) p.stamps[(long long)blockIdx.x * 64 + 51] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -377,7 +476,7 @@ __global__ void __launch_bounds__(512) conv3d_v5_kernel(V4Params p) {
   int pc = pt.c0;
   auto issue_next = [&](int buf) -> bool {
     if (pit >= ntile) return false;
-    if (!V5_DIAG(1)) v4_issue_halo<T, MODE>(p, pt, V5_PHYS(pt, pc), smem + buf * C::HALO_B, h, lane);
+    if (!V5_DIAG(1)) v4_issue_halo<T, HM>(p, pt, V5_PHYS(pt, pc), smem + buf * C::HALO_B, h, lane);
     if constexpr (GN) {
       if (lane < 32)
         __builtin_amdgcn_global_load_lds(
@@ -435,8 +534,11 @@ __global__ void __launch_bounds__(512) conv3d_v5_kernel(V4Params p) {
       (void)x0; (void)y0; (void)z0; (void)buf;
     }
   };
-  const long long HW = (long long)p.H * p.W, VV = (long long)p.D * HW;
-  const unsigned rowb = (unsigned)p.W * (unsigned)p.cout * 2u, planeb = (unsigned)HW * (unsigned)p.cout * 2u;
+  // output voxels per batch, and the byte steps of a tile's next line / plane in the output (phase
+  // instance: the 2D x 2H x 2W grid, every second line / plane)
+  const long long HW = (long long)p.H * p.W, VV = (long long)p.D * HW * (PH ? 8 : 1);
+  const unsigned rowb = (unsigned)p.W * (unsigned)p.cout * (PH ? 8u : 2u);
+  const unsigned planeb = (unsigned)HW * (unsigned)p.cout * (PH ? 16u : 2u);
   float s1[8], s2[8];   // this lane's statistics over both drain parts of a tile
   bool wg_final = false;   // stats_wg: the drain of this workgroup's last tile (writes the row)
   u32x4 dq[8];          // a drain slice's output rows and their byte offsets (drain -> drain_put)
@@ -484,8 +586,11 @@ __global__ void __launch_bounds__(512) conv3d_v5_kernel(V4Params p) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
     }
-    const unsigned obase =
-        ((unsigned)((tt.z0 * p.H + tt.y0) * p.W) + (unsigned)ox) * (unsigned)p.cout * 2u + (unsigned)(tt.ct * 64 + 8 * q) * 2u;
+    const unsigned ovox =
+        PH ? (unsigned)(((2 * tt.z0 + (tt.ph >> 2)) * (2 * p.H) + 2 * tt.y0 + ((tt.ph >> 1) & 1)) * (2 * p.W)) +
+                 (unsigned)(2 * ox + (tt.ph & 1))
+           : (unsigned)((tt.z0 * p.H + tt.y0) * p.W) + (unsigned)ox;
+    const unsigned obase = ovox * (unsigned)p.cout * 2u + (unsigned)(tt.ct * 64 + 8 * q) * 2u;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       if (k < k0 || k >= k1) continue;
@@ -550,7 +655,15 @@ __global__ void __launch_bounds__(512) conv3d_v5_kernel(V4Params p) {
                   run[ct * 64 + lane];
           }
         } else {
-          const long long pidx = ((long long)tt.b * tiles + tt.sl) * p.cout + tt.ct * 64 + lane;
+          // per tile: row = the tile (phase instance: the output brick (2 sx + px, 2 sy + py, 2 sz + pz)
+          // of the 2 tx x 2 ty x 2 tz rows; the host grants it only where that is cwdm_conv3d_parts)
+          long long row = (long long)tt.b * tiles + tt.sl;
+          if constexpr (PH) {
+            const int sx = tt.sl % p.tx, sy = (tt.sl / p.tx) % p.ty, sz = tt.sl / (p.tx * p.ty);
+            row = (long long)tt.b * tiles * 8 +
+                  ((2 * sz + (tt.ph >> 2)) * (2 * p.ty) + 2 * sy + ((tt.ph >> 1) & 1)) * (2 * p.tx) + 2 * sx + (tt.ph & 1);
+          }
+          const long long pidx = row * p.cout + tt.ct * 64 + lane;
           *reinterpret_cast<float2*>(p.stats + pidx * 2) = make_float2(su, sq);
         }
       }
@@ -590,7 +703,7 @@ __global__ void __launch_bounds__(512) conv3d_v5_kernel(V4Params p) {
     int pc = pt.c0;
     bool chk = false;   // the cursor's tile reads a range some other workgroup may still write
     auto issue_aa = [&](int buf) {
-      v4_issue_halo<T, MODE, C::HVP * 16, true>(p, pt, pc, smem + buf * C::HALO_B, h, lane);
+      v4_issue_halo<T, HM, C::HVP * 16, true>(p, pt, pc, smem + buf * C::HALO_B, h, lane);
       if (pc + 1 < pt.c1) {
         ++pc;
       } else if (pit + 1 < ntile) {
@@ -1172,6 +1285,9 @@ int v5_mode() {
 std::atomic<int> g_v5_grid{0};
 std::atomic<int> g_v5_aa{env_int("CWDM_V5_AA", 1)};
 std::atomic<int> g_v5_aa_launches{0};
+// the phase instance for upsampling convs that bring phase weights (cwdm_debug_up_phase)
+std::atomic<int> g_up_phase{env_not0("CWDM_UP_PHASE") ? 1 : 0};
+std::atomic<int> g_up_phase_launches{0};
 std::atomic<int> g_v5_aa_extra{0};
 std::atomic<int> g_v5_aa_spin{0};
 // the U-Net plan asks for per-workgroup GroupNorm partials (V4Params::stats_wg) around its convs and
@@ -1247,17 +1363,41 @@ bool v5_eligible(const cwdm_conv3d_desc* d, bool gn) {
   if (d->D * d->H * d->W * d->cout * 2 >= 0xFFFFE000LL) return false;
   if (d->a_c0 + d->a_c1 < 32) return false;   // >= 2 chunks per tile: a tile's drain spans two chunks
   if (gbwd_grid_ok(d)) return false;   // the backward's fused dgrad instance is v4's
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return 256;
-    return n > 0 ? n : 256;
-  }();
+  const int ncu = v5_ncu();
   // tiles per CU below which v4 (two workgroups per CU) keeps the conv (env
   // CWDM_V5_MIN_TPC, A/B knob; 1 since r04: config 5's 56^3 64-channel convs,
   // 392 tiles, 57 -> 53 us on v5)
   static const double min_tpc = env_double("CWDM_V5_MIN_TPC", 1.0);
   return path == 2 || (double)v4_items(d) >= min_tpc * ncu;
+}
+
+// the persistent grid of a plain launch: one workgroup per CU (or the debug cap), never more than the items
+namespace {
+unsigned v5_grid(long long nblk) {
+  const int cap = g_v5_grid.load(std::memory_order_relaxed);
+  return (unsigned)std::min<long long>(nblk, cap > 0 ? cap : v5_ncu());
+}
+}  // namespace
+
+// The phase instance (conv3d_v5_kernel<T, 2, false>) takes an upsampling conv the gather instance
+// (MODE 1) would run -- 16-bit, no residual, no 1x1 skip product -- when its phase weights came along
+// and the SOURCE grid tiles (W / 2 >= kWideMinW, H / 2 and D / 2 multiples of 4).  Statistics: per
+// workgroup wherever the plan asks for them and the rows fit; per tile one row per (source tile,
+// phase), laid out as the 2 tx x 2 ty x 2 tz output bricks -- only where those are the rows the caller
+// holds (cwdm_conv3d_parts of the output grid: ceil(W / 32) == 2 ceil(W / 64)), else the gather path.
+bool v5_phase_ok(const cwdm_conv3d_desc* d, int rmode) {
+  if (!d->a_w_phase || !g_up_phase.load(std::memory_order_relaxed)) return false;
+  if (!dtype_half(d->dtype) || d->a_mode != 1 || d->b_w || rmode != -1 || d->res_mode != -1) return false;
+  if (!v5_eligible(d, false)) return false;
+  const int64_t SD = d->D / 2, SH = d->H / 2, SW = d->W / 2;
+  if (SW < kWideMinW || SH % 4 || SD % 4) return false;
+  if (d->stats) {
+    const int64_t stx = (SW + 31) / 32, otx = (d->W + 31) / 32, otiles = otx * (d->H / 4) * (d->D / 4);
+    const long long nblk = (long long)d->B * stx * (SH / 4) * (SD / 4) * (d->cout / 64) * 8;
+    const bool wg = g_stats_wg && d->B == 1 && d->cout / 64 <= 2 && (long long)v5_grid(nblk) <= otiles;
+    if (!wg && otx != 2 * stx) return false;
+  }
+  return true;
 }
 
 // sources a0 (c0 channels; chunk-major if a0_cm) and a1 (c1, channels-last);
@@ -1304,23 +1444,27 @@ int v5_aa_units(const cwdm_conv3d_desc* d, int* lead) {
 }
 
 int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
-              const float* agn, const void* res, int rmode, hipStream_t s, const V5Aa* aa) {
+              const float* agn, const void* res, int rmode, hipStream_t s, const V5Aa* aa, bool phase) {
   const int esz = dtype_size(d->dtype);
   const int ck = 32 / esz;
   const int64_t SV = d->a_mode == 1 ? d->D * d->H * d->W / 8 : d->D * d->H * d->W;
   CWDM_REQUIRE(!agn || !a0_cm, CWDM_E_INVALID, "conv3d_v5: GroupNorm applies to raw channels-last sources only");
+  CWDM_REQUIRE(!phase || (d->a_w_phase && d->a_mode == 1 && !agn && !aa && rmode < 0 && dtype_half(d->dtype)),
+               CWDM_E_INVALID, "conv3d_v5: phase arguments");
   V4Params p{};
   p.B = (int)d->B; p.D = (int)d->D; p.H = (int)d->H; p.W = (int)d->W;
+  // the phase instance tiles the source grid (the output is 2D x 2H x 2W)
+  if (phase) { p.D /= 2; p.H /= 2; p.W /= 2; }
   p.tx = (p.W + 31) / 32; p.ty = p.H / 4; p.tz = p.D / 4;
   p.cout = d->cout; p.nct = d->cout / 64;
   p.nch0 = c0 / ck; p.nch = (c0 + c1) / ck;
   p.a0 = a0; p.ac0 = c0; p.a1 = a1; p.ac1 = c1;
   p.a0_bstride = SV * c0 * esz; p.a1_bstride = SV * c1 * esz;
   p.a0_bytes = (unsigned)(SV * c0 * esz); p.a1_bytes = (unsigned)(SV * c1 * esz);
-  p.amode = d->a_mode;
+  p.amode = phase ? 0 : d->a_mode;
   p.a0_cm = a0_cm;
   p.a0_cvox = (int)SV;
-  p.aw = reinterpret_cast<const unsigned char*>(d->a_w);
+  p.aw = reinterpret_cast<const unsigned char*>(phase ? d->a_w_phase : d->a_w);
   p.bias = d->bias; p.bias_bs = d->bias_bstride;
   p.res = res; p.rmode = rmode;
   p.out = d->out;
@@ -1346,29 +1490,26 @@ int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
   p.diag = diag;
 #endif
   p.stamps = g_stamps.load(std::memory_order_relaxed);
-  const long long nblk = (long long)p.B * p.tx * p.ty * p.tz * p.nct;
+  const long long nblk = (long long)p.B * p.tx * p.ty * p.tz * p.nct * (phase ? 8 : 1);
+  CWDM_REQUIRE(nblk < (1LL << 31), CWDM_E_UNSUPPORTED, "conv3d_v5: too many work items");
   p.nblk = (int)nblk;
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return 256;
-    return n > 0 ? n : 256;
-  }();
-  const int cap = g_v5_grid.load(std::memory_order_relaxed);
-  const dim3 grid(aa ? (unsigned)v5_aa_grid(nblk) : (unsigned)std::min<long long>(nblk, cap > 0 ? cap : ncu));
+  const dim3 grid(aa ? (unsigned)v5_aa_grid(nblk) : v5_grid(nblk));
   // per-workgroup statistics rows (16-bit kernel, batch 1, <= 2 channel tiles, no more rows than the
-  // per-tile layout has): the finalize then reduces gridDim.x rows instead of one per tile
-  if (g_stats_wg && d->stats && p.B == 1 && p.nct <= 2 &&
-      (long long)grid.x <= (long long)p.tx * p.ty * p.tz) {
+  // per-tile layout has -- the tiles of the OUTPUT grid, which the caller sized its rows by): the
+  // finalize then reduces gridDim.x rows instead of one per tile
+  const long long otiles = phase ? ((d->W + 31) / 32) * (d->H / 4) * (d->D / 4) : (long long)p.tx * p.ty * p.tz;
+  if (g_stats_wg && d->stats && p.B == 1 && p.nct <= 2 && (long long)grid.x <= otiles) {
     p.stats_wg = 1;
     g_stats_rows = grid.x;
   }
+  // (v5_eligible never grants the in-LDS GroupNorm to an upsampling conv: its halo repeats every source voxel 8x)
+  CWDM_REQUIRE(!(agn && p.amode == 1 && dtype_half(d->dtype)), CWDM_E_UNSUPPORTED,
+               "conv3d_v5: GroupNorm in LDS on an upsampling conv");
   prof_begin(s);
   auto go = [&](auto tag) {
     using T = decltype(tag);
-    if (agn) {
-      if (p.amode == 1) hipLaunchKernelGGL((conv3d_v5_kernel<T, 1, true>), grid, dim3(512), 0, s, p);
-      else hipLaunchKernelGGL((conv3d_v5_kernel<T, 0, true>), grid, dim3(512), 0, s, p);
+    if (agn) {   // (never an upsampling conv: v5_eligible, checked above)
+      hipLaunchKernelGGL((conv3d_v5_kernel<T, 0, true>), grid, dim3(512), 0, s, p);
     } else {
       if (p.amode == 1) hipLaunchKernelGGL((conv3d_v5_kernel<T, 1, false>), grid, dim3(512), 0, s, p);
       else hipLaunchKernelGGL((conv3d_v5_kernel<T, 0, false>), grid, dim3(512), 0, s, p);
@@ -1383,6 +1524,10 @@ int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
       if (p.amode == 1) hipLaunchKernelGGL((conv3d_v5s_kernel<1, false>), grid, dim3(512), 0, s, p);
       else hipLaunchKernelGGL((conv3d_v5s_kernel<0, false>), grid, dim3(512), 0, s, p);
     }
+  } else if (phase) {
+    g_up_phase_launches.fetch_add(1, std::memory_order_relaxed);
+    if (d->dtype == CWDM_BF16) hipLaunchKernelGGL((conv3d_v5_kernel<bf16_t, 2, false>), grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((conv3d_v5_kernel<f16_t, 2, false>), grid, dim3(512), 0, s, p);
   } else if (aa) {
     g_v5_aa_launches.fetch_add(1, std::memory_order_relaxed);
     auto go_aa = [&](auto tag) {
@@ -1398,17 +1543,19 @@ int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
   } else {
     go(f16_t{});
   }
-  prof_end(s, 2.0 * p.B * p.D * p.H * p.W * (double)p.cout * 27.0 * (c0 + c1));
+  // (the flops executed: the phase instance runs 8 folded taps per output voxel, not 27)
+  prof_end(s, phase ? 2.0 * d->B * d->D * d->H * d->W * (double)p.cout * 8.0 * (c0 + c1)
+                    : 2.0 * p.B * p.D * p.H * p.W * (double)p.cout * 27.0 * (c0 + c1));
   CWDM_LAUNCHED();
   return CWDM_OK;
 }
 
+template __global__ void conv3d_v5_kernel<bf16_t, 2, false>(V4Params);
+template __global__ void conv3d_v5_kernel<f16_t, 2, false>(V4Params);
 template __global__ void conv3d_v5_kernel<bf16_t, 0, true>(V4Params);
-template __global__ void conv3d_v5_kernel<bf16_t, 1, true>(V4Params);
 template __global__ void conv3d_v5_kernel<bf16_t, 0, false>(V4Params);
 template __global__ void conv3d_v5_kernel<bf16_t, 1, false>(V4Params);
 template __global__ void conv3d_v5_kernel<f16_t, 0, true>(V4Params);
-template __global__ void conv3d_v5_kernel<f16_t, 1, true>(V4Params);
 template __global__ void conv3d_v5_kernel<f16_t, 0, false>(V4Params);
 template __global__ void conv3d_v5_kernel<f16_t, 1, false>(V4Params);
 template __global__ void conv3d_v5_kernel<bf16_t, 0, false, 4>(V4Params);
@@ -1425,6 +1572,19 @@ template __global__ void conv3d_v5s_kernel<1, false>(V4Params);
 extern "C" int cwdm_debug_v5_aa(int on) {
   if (on < 0) return cwdm::g_v5_aa_launches.load(std::memory_order_relaxed);
   return cwdm::g_v5_aa.exchange(on > 2 ? 2 : on);
+}
+
+extern "C" int cwdm_debug_up_phase(int on) {
+  if (on < 0) return cwdm::g_up_phase_launches.load(std::memory_order_relaxed);
+  return cwdm::g_up_phase.exchange(on ? 1 : 0);
+}
+
+extern "C" int64_t cwdm_debug_stats_wg(int on) {
+  if (on < 0) return cwdm::g_stats_rows;
+  const int prev = cwdm::g_stats_wg;
+  cwdm::g_stats_wg = on ? 1 : 0;
+  cwdm::g_stats_rows = 0;
+  return prev;
 }
 
 extern "C" int cwdm_debug_v5_aa_timeout(int extra, int spin) {

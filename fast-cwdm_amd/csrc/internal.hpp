@@ -66,6 +66,9 @@ struct ActKeepScope {
 // conv3d_v5.hip: the warp-specialised conv
 bool v5_eligible(const cwdm_conv3d_desc* d, bool gn);
 int v5_aa_units(const cwdm_conv3d_desc* d, int* lead);
+// the phase instance takes this upsampling conv (cwdm_conv3d_desc.a_w_phase; rmode: the residual
+// mode after the 1x1 skip pre-pass)
+bool v5_phase_ok(const cwdm_conv3d_desc* d, int rmode);
 extern thread_local int g_stats_wg;         // per-workgroup GroupNorm partials wanted
 extern thread_local int64_t g_stats_rows;   // ... and the rows the last launch wrote (0: per tile)
 

@@ -58,6 +58,7 @@ struct ConvStep {
   int skip_conv = -1;           // conv1 of a block with a 1x1 skip: index of the block's conv2
   int64_t wsplit_off = -1;      // accurate fast mode: split-bf16 packed weights (cwdm_conv3d_pack_split), -1 none
   int64_t hsplit_off = -1;      // accurate fast mode, output head: K-expanded bf16 weights [hi | hi | lo] (head_split3_pack)
+  int64_t wphase_off = -1;      // 16-bit upsampling convs: phase weights (cwdm_conv3d_pack_phase), -1 none
   int64_t xsplit_off = -1;      // accurate fast mode, small grids (level >= 2): the same for the bf16 small-grid kernel
   int64_t xsplit_sk_off = -1;   //   and for its 1x1 skip (k = 1)
   int s2 = 0;                   // stride-2 conv (Downsample.op) over a space-to-depth input: cin_a = 8 x its channels
@@ -539,6 +540,11 @@ void build(cwdm_unet* u) {
     cs.w_off = take(cwdm_conv3d_packed_bytes(cs.cout, cs.cin_a, 3, c.dtype));
     if (c.mfma_split && c.dtype == CWDM_F32 && !cs.s2 && cs.cout % 64 == 0 && cs.cin_a % 16 == 0)
       cs.wsplit_off = take(cwdm_conv3d_packed_split_bytes(cs.cout, cs.cin_a));
+    // an upsampling conv's phase weights, by the channel rule (whether a forward's grid takes the
+    // phase path is decided per launch: cwdm_conv3d_desc.a_w_phase)
+    if (dtype_half(c.dtype) && cs.amode == 1 && !cs.s2 && cs.ws_p < 0 && cs.rmode == -1 && cs.cout % 64 == 0 &&
+        cs.cin_a % 16 == 0 && cs.cin_a >= 32)
+      cs.wphase_off = take(cwdm_conv3d_packed_phase_bytes(cs.cout, cs.cin_a, c.dtype));
     if (c.mfma_split && c.dtype == CWDM_F32 && &cs == &u->convs[u->head_c] && cs.a1 < 0 && cs.amode == 0 &&
         cs.gn >= 0 && cs.cout <= 16 && cs.cin_a % 32 == 0 && 3 * cs.cin_a <= 256) {
       cs.hsplit_off = take(cwdm_conv3d_packed_bytes(cs.cout, 3 * cs.cin_a, 3, CWDM_BF16));
@@ -926,6 +932,9 @@ extern "C" int cwdm_unet_pack(const cwdm_unet* uc, const float* const* P, void* 
       } else if ((rc = cwdm_conv3d_pack(P[cs.w_p], cs.cout, cs.cin_a, 3, u->cfg.dtype, base + cs.w_off, stream))) {
         return rc;
       }
+      if (cs.wphase_off >= 0 &&
+          (rc = cwdm_conv3d_pack_phase(P[cs.w_p], cs.cout, cs.cin_a, u->cfg.dtype, base + cs.wphase_off, stream)))
+        return rc;
       if (cs.wsplit_off >= 0 &&
           (rc = cwdm_conv3d_pack_split(P[cs.w_p], cs.cout, cs.cin_a, base + cs.wsplit_off, stream)))
         return rc;
@@ -1117,6 +1126,7 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
     d.a_gn = cs.gn >= 0 ? reinterpret_cast<const float*>(wb + L.ss_off[cs.gn]) : nullptr;
     d.a_w = pk + cs.w_off;
     d.a_w_split = cs.wsplit_off >= 0 ? pk + cs.wsplit_off : nullptr;
+    d.a_w_phase = cs.wphase_off >= 0 ? pk + cs.wphase_off : nullptr;
     if (cs.ws_p >= 0) {
       d.b0 = tptr(cs.sb0); d.b_c0 = u->tensors[cs.sb0].channels;
       d.b1 = tptr(cs.sb1); d.b_c1 = cs.sb1 >= 0 ? u->tensors[cs.sb1].channels : 0;

@@ -65,6 +65,7 @@ class ConvDesc(ctypes.Structure):
         ("out1", vp), ("out_c0", ctypes.c_int),
         ("accumulate", ctypes.c_int),
         ("a_w_split", vp),
+        ("a_w_phase", vp),
     ]
 
 
@@ -137,6 +138,8 @@ _PROTOS = {
     "cwdm_conv3d_pack": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
     "cwdm_conv3d_packed_split_bytes": (i64, [ctypes.c_int, ctypes.c_int]),
     "cwdm_conv3d_pack_split": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "cwdm_conv3d_packed_phase_bytes": (i64, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "cwdm_conv3d_pack_phase": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
     "cwdm_conv3d_pack_dgrad": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
     "cwdm_conv3d_parts": (i64, [ctypes.c_int, i64, i64, i64, ctypes.c_int]),
     "cwdm_space_to_depth": (ctypes.c_int, [vp, ctypes.c_int, i64, i64, i64, i64, ctypes.c_int, vp, ctypes.c_int,
@@ -152,6 +155,8 @@ _PROTOS = {
     "cwdm_conv3d_set_path": (ctypes.c_int, [ctypes.c_int]),
     "cwdm_debug_v5_grid": (ctypes.c_int, [ctypes.c_int]),
     "cwdm_debug_v5_aa": (ctypes.c_int, [ctypes.c_int]),
+    "cwdm_debug_up_phase": (ctypes.c_int, [ctypes.c_int]),
+    "cwdm_debug_stats_wg": (i64, [ctypes.c_int]),
     "cwdm_debug_v5_aa_timeout": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "cwdm_device_status": (ctypes.c_int, [ctypes.c_int]),
     "cwdm_debug_gn_fin_apply": (ctypes.c_int, [vp, i64, ctypes.c_int, vp, i64, ctypes.c_int, vp, vp, ctypes.c_int,

@@ -296,6 +296,16 @@ typedef struct {
                                is ~2^-18 of each product, about 64x fp32 epsilon: see DESIGN.md §4)
                                where the shape takes the warp-specialised kernel (a_c0, a_c1
                                multiples of 16); fp32 in, fp32 out */
+  const void* a_w_phase;    /* 16-bit a_mode 1 convs (optional): cwdm_conv3d_pack_phase weights -- the
+                               nearest-x2 upsampling conv runs as eight 2x2x2 phase convs on the source
+                               grid, in one launch of the warp-specialised kernel (8 / 27 of the MACs).
+                               Honoured where the SOURCE grid takes that kernel (source W >= 24, H % 4,
+                               D % 4 == 0, cout % 64 == 0, >= 32 input channels), without a 1x1 segment
+                               or residual; elsewhere, and when NULL, the 27-tap path runs as before.
+                               With stats set on a lone call the phase path also needs the per-tile rows
+                               to be the caller's cwdm_conv3d_parts rows: ceil(W / 32) == 2 ceil(W / 64)
+                               (an 80-wide output, 3 x tiles against 2 x 2 phase rows, stays on the
+                               27-tap path) */
 } cwdm_conv3d_desc;
 int64_t cwdm_conv3d_packed_bytes(int cout, int cin, int ksize, int dtype);
 /* Split-bf16 weights of a 3x3x3 fp32 conv (cout % 64 == 0, cin % 16 == 0) for
@@ -305,6 +315,16 @@ int64_t cwdm_conv3d_packed_split_bytes(int cout, int cin);
 int cwdm_conv3d_pack_split(const float* w_oidhw, int cout, int cin, void* packed, cwdm_stream_t stream);
 int cwdm_conv3d_pack(const float* w_oidhw, int cout, int cin, int ksize, int dtype,
                      void* packed, cwdm_stream_t stream);
+/* Phase weights of a 3x3x3 conv over a nearest-x2 upsampled input (bf16 / fp16, cout % 64 == 0,
+ * cin % 16 == 0) for cwdm_conv3d_desc.a_w_phase.  Output voxel 2 i + p (p = 0, 1 per axis) reads the
+ * source voxels i + p - 1 + t, t = 0, 1, with the weights [w0, w1 + w2] (p = 0) / [w0 + w1, w2]
+ * (p = 1): per phase 4 pz + 2 py + px a 2x2x2 conv, tap 4 tz + 2 ty + tx.  The 1, 2, 4 or 8 fp32
+ * master weights of a folded tap are summed in fp32 (kz, then ky, then kx ascending) and rounded
+ * once.  Layout [phase 8][cout tile][chunk][8 taps][2048 B], a tap's 2048 bytes as in
+ * cwdm_conv3d_pack: 64 / 27 of cwdm_conv3d_packed_bytes(cout, cin, 3, dtype). */
+int64_t cwdm_conv3d_packed_phase_bytes(int cout, int cin, int dtype);
+int cwdm_conv3d_pack_phase(const float* w_oidhw, int cout, int cin, int dtype, void* packed,
+                           cwdm_stream_t stream);
 /* Packs the input-gradient (dgrad) conv of a (cin -> cout) conv: a (cout -> cin)
  * conv with spatially flipped, transposed weights (the backward of Conv3d's
  * input, stride 1, pad 1).  Its input channels (cout) are zero-padded up to the
@@ -374,6 +394,20 @@ int cwdm_debug_v5_grid(int n);
  * for any eligible conv, 0 off; returns the previous setting.  -1: changes
  * nothing, returns the number of apply-ahead launches so far. */
 int cwdm_debug_v5_aa(int on);
+
+/* Diagnostics / tests only: the phase path of the upsampling convs
+ * (cwdm_conv3d_desc.a_w_phase): 1 on (default; env CWDM_UP_PHASE=0 starts it
+ * off), 0 off (the 27-tap gather path); returns the previous setting.  -1:
+ * changes nothing, returns the number of phase launches so far. */
+int cwdm_debug_up_phase(int on);
+
+/* Diagnostics / tests only: ask lone cwdm_conv3d_forward calls of this thread for
+ * the per-workgroup statistics layout the U-Net plan uses around its convs (row w
+ * of stats = the sums over the tiles workgroup w ran; granted by the
+ * warp-specialised conv for batch 1, cout <= 128, no more workgroups than
+ * cwdm_conv3d_parts rows): 1 on, 0 off, returns the previous setting.  -1: changes
+ * nothing, returns the rows the last launch of this thread wrote that way (0: per tile). */
+int64_t cwdm_debug_stats_wg(int on);
 
 /* Diagnostics / tests only: make every apply-ahead counter wait require `extra`
  * arrivals beyond the grid and give up after `spin` s_sleep rounds (0, 0 =

@@ -24,6 +24,7 @@ CASES = {
     "L0_64_64_gn_skip192": (128, 64, 0, 64, 0, True, 192, -1),
     "L0_128_128_up": (128, 128, 0, 128, 1, True, 0, -1),
     "L0_128_128_gn": (128, 128, 0, 128, 0, True, 0, -1),
+    "L1_128_128_up": (64, 128, 0, 128, 1, True, 0, -1),
     "L0_192_64_cat": (128, 128, 64, 64, 0, True, 0, -1),
     "L0_64_8_out": (128, 64, 0, 8, 0, True, 0, -1),
     "L0_64_8_out_nogn": (128, 64, 0, 8, 0, False, 0, -1),
@@ -85,6 +86,11 @@ def run_case(name, spec, iters, dtype):
     d.a_mode = amode
     d.a_gn = gnb.data_ptr() if gn else None
     d.a_w = pw.data_ptr()
+    if amode == 1 and dtype != _lib.CWDM_F32:   # the phase weights (env CWDM_UP_PHASE=0: the gather path)
+        pp = torch.empty(L.cwdm_conv3d_packed_phase_bytes(cout, cin, dtype), dtype=torch.uint8, device=dev)
+        check(L.cwdm_conv3d_pack_phase(ctypes.c_void_p(w.data_ptr()), cout, cin, dtype, ctypes.c_void_p(pp.data_ptr()),
+                                       None))
+        d.a_w_phase = pp.data_ptr()
     if cb:
         d.b0, d.b_c0, d.b_w = b0.data_ptr(), cb, pb.data_ptr()
     d.bias, d.bias_bstride = bias.data_ptr(), 0
