@@ -26,7 +26,7 @@ struct Param { std::string name; std::vector<int64_t> shape; int64_t numel() con
 struct Tensor {
   int level, channels;
   int stats_kind = 0;  // producer of its (sum, sum^2) parts: 0 conv epilogue, 1 / 2 cwdm_haar_nd over its own /
-                       // the half grid (analysis / synthesis output), -1 none (never GroupNorm'd)
+                       // the half grid (analysis / synthesis output), 3 cwdm_skip_avg, -1 none (never GroupNorm'd)
 };
 
 struct GnStep {
@@ -81,7 +81,12 @@ struct HaarStep {  // WavUNetModel resampling / input pyramid (cwdm_haar_nd, wav
   int level;                        // the coarse grid's level
 };
 
-struct Step { int kind; int idx; };  // kind 0 = gn, 1 = conv, 2 = pool pre-pass, 3 = space-to-depth, 4 = haar
+struct AvgStep {  // additive skip (cwdm_skip_avg, skip_avg.hip): out = (a + b) / 2
+  int a, b, out, level, channels;
+};
+
+struct Step { int kind; int idx; };  // kind 0 = gn, 1 = conv, 2 = pool pre-pass, 3 = space-to-depth, 4 = haar,
+                                     // 5 = additive skip
 
 // one ResBlock, for the backward (reverse order) and the gradient segments
 struct Block {
@@ -94,6 +99,7 @@ struct Block {
   int p_begin, p_end;         // parameter index range
   int emb_k;                  // index into emb_rows_*
   int hh = -1, hx = -1;       // WavUNetModel down / up blocks: HaarSteps of h (+ emb) and of x (x_upd)
+  int avg = -1;               // additive skips: the AvgStep that produced x0 (its adjoint ends the block's backward)
 };
 
 }  // namespace
@@ -122,6 +128,7 @@ struct cwdm_unet {
   std::vector<PoolStep> pools;
   std::vector<S2dStep> s2ds;
   std::vector<HaarStep> haars;
+  std::vector<AvgStep> avgs;
   std::vector<Step> steps;
   struct Alias { std::string name; int owner, before; };
   std::vector<Alias> aliases;     // WavUNetModel: second state_dict name of a reused parameter; before = the
@@ -499,8 +506,21 @@ void build(cwdm_unet* u) {
     for (int i = 0; i <= c.num_res_blocks; ++i) {
       int skip = stack.back();
       stack.pop_back();
-      h = resblock("output_blocks." + std::to_string(idx) + ".0", h, skip, mc * mult, 0);
-      ch = mc * mult;
+      if (c.additive_skips) {
+        // h = (h + skip) / 2, then an ordinary single-source ResBlock to the channels of the next
+        // skip left on the stack (unet.py:664-666), so h always matches the skip it is averaged with
+        AvgStep as{h, skip, -1, level, u->tensors[skip].channels};
+        as.out = new_tensor(level, as.channels);
+        u->tensors[as.out].stats_kind = 3;
+        u->avgs.push_back(as);
+        u->steps.push_back({5, (int)u->avgs.size() - 1});
+        ch = stack.empty() ? mc : u->tensors[stack.back()].channels;
+        h = resblock("output_blocks." + std::to_string(idx) + ".0", as.out, -1, ch, 0);
+        u->blocks.back().avg = (int)u->avgs.size() - 1;
+      } else {
+        h = resblock("output_blocks." + std::to_string(idx) + ".0", h, skip, mc * mult, 0);
+        ch = mc * mult;
+      }
       u->trace.push_back(h); u->trace_level.push_back(level);
       if (l && i == c.num_res_blocks) {
         const std::string p = "output_blocks." + std::to_string(idx) + ".1";
@@ -698,6 +718,7 @@ Layout layout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) {
     const int64_t parts = t.stats_kind < 0    ? 0
                           : t.stats_kind == 1 ? cwdm_haar_nd_parts(d, h, w)
                           : t.stats_kind == 2 ? cwdm_haar_nd_parts(d / 2, h / 2, w / 2)
+                          : t.stats_kind == 3 ? cwdm_skip_avg_parts(d * h * w)
                                               : cwdm_conv3d_parts(u->cfg.dtype, d, h, w, t.channels);
     L.s_parts.push_back(parts);
     L.s_off.push_back(take(B * parts * t.channels * 2 * 4));
@@ -798,6 +819,8 @@ extern "C" int cwdm_unet_create(const cwdm_unet_config* cfg, cwdm_unet** plan) {
                  "cwdm_unet_create: level channels must be multiples of 32 (and of the chunk)");
     CWDM_REQUIRE(ch % cfg->num_groups == 0, CWDM_E_INVALID, "cwdm_unet_create: channels not divisible by groups");
   }
+  CWDM_REQUIRE(!(cfg->additive_skips && cfg->use_freq), CWDM_E_UNSUPPORTED,
+               "cwdm_unet_create: additive_skips with use_freq (WavUNetModel has no concatenation to replace)");
   if (cfg->use_freq) {
     // WavUNetModel as script_util.create_model builds it (:268-292)
     CWDM_REQUIRE(cfg->resblock_updown, CWDM_E_UNSUPPORTED,
@@ -1110,6 +1133,15 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
       a.bias_bstride = u->R;
       a.stats = hs.stats ? reinterpret_cast<float*>(wb + L.s_off[hs.out]) : nullptr;
       if ((rc = cwdm_haar_nd(&a, stream))) return rc;
+      continue;
+    }
+    if (st.kind == 5) {
+      const auto& as = u->avgs[st.idx];
+      const int lv = as.level;
+      if ((rc = cwdm_skip_avg(tptr(as.a), tptr(as.b), wb + L.t_off[as.out],
+                              reinterpret_cast<float*>(wb + L.s_off[as.out]), u->cfg.dtype, B,
+                              (D >> lv) * (H >> lv) * (W >> lv), as.channels, stream)))
+        return rc;
       continue;
     }
     if (st.kind == 0) {
@@ -1773,6 +1805,15 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
       const int64_t Vo = vox(lout);
       const int o = c2.out, h1 = c1.out;
       const int cout = c2.cout;
+      // additive skips: the block's input is (h + skip) / 2; once its gradient is complete, the adjoint
+      // hands half of it to h and to the skip (whose encoder consumer runs later and accumulates)
+      auto avg_bwd = [&]() -> int {
+        if (bk.avg < 0) return CWDM_OK;
+        const auto& as = u->avgs[bk.avg];
+        const int aa = take_acc(as.a), ab = take_acc(as.b);
+        return cwdm_skip_avg_bwd(grd(as.out), grd(as.a), aa, grd(as.b), ab, dt, B, vox(as.level), as.channels,
+                                 stream);
+      };
       // ---- conv2 (+ skip / residual)
       if ((rc = cwdm_channel_sum(grd(o), dt, B, Vo, cout, cout, nullptr, 0, GR(c2.b_p),
                                  c2.wsb_p >= 0 ? GR(c2.wsb_p) : nullptr, gb + G.chs, G.chs_bytes, stream)))
@@ -1882,9 +1923,11 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
         cwdm::GapplyFuse gf{};
         gf.x0 = act(bk.x0); gf.x1 = act(bk.x1); gf.du = tmp; gf.ss = ss_of(bk.g1); gf.coef = coef;
         if ((rc = skip_dgrad(&gf, false))) return rc;
+        if ((rc = avg_bwd())) return rc;
         continue;
       }
       if ((rc = gn_bwd(bk.g1, bk.x0, bk.x1, bk.updown == 1 ? 1 : (bk.updown == 2 ? 2 : 0), &pre1))) return rc;
+      if ((rc = avg_bwd())) return rc;
       continue;
     }
     // conv_in + time_embed

@@ -93,7 +93,7 @@ class UNetConfig(ctypes.Structure):
         ("num_levels", ctypes.c_int), ("channel_mult", ctypes.c_int * 8),
         ("num_groups", ctypes.c_int), ("dtype", ctypes.c_int),
         ("resblock_updown", ctypes.c_int), ("use_freq", ctypes.c_int),
-        ("mfma_split", ctypes.c_int),
+        ("mfma_split", ctypes.c_int), ("additive_skips", ctypes.c_int),
     ]
 
 
@@ -189,6 +189,10 @@ _PROTOS = {
                                             ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "cwdm_haar_nd_parts": (i64, [i64, i64, i64]),
     "cwdm_haar_nd": (ctypes.c_int, [ctypes.POINTER(HaarNdDesc), vp]),
+    "cwdm_skip_avg_parts": (i64, [i64]),
+    "cwdm_skip_avg": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, i64, i64, ctypes.c_int, vp]),
+    "cwdm_skip_avg_bwd": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, i64, i64,
+                                         ctypes.c_int, vp]),
     "cwdm_wavelet2_analysis": (ctypes.c_int, [vp, i64, i64, i64, i64, vp, ctypes.c_int, i64, i64, ctypes.c_int, vp]),
     "cwdm_wavelet2_synthesis": (ctypes.c_int, [vp, i64, i64, i64, i64, i64, i64, ctypes.c_int, vp, vp]),
     "cwdm_unet_param_info": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(i64),

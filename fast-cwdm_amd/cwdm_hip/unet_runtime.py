@@ -30,7 +30,7 @@ def parse_dtype(d):
 
 class UNetPlan:
     def __init__(self, in_channels, model_channels, out_channels, num_res_blocks, channel_mult, num_groups,
-                 dtype="fp32", resblock_updown=True, use_freq=False):
+                 dtype="fp32", resblock_updown=True, use_freq=False, additive_skips=False):
         cfg = _lib.UNetConfig()
         cfg.in_channels, cfg.model_channels, cfg.out_channels = in_channels, model_channels, out_channels
         cfg.num_res_blocks, cfg.num_levels = num_res_blocks, len(channel_mult)
@@ -43,6 +43,7 @@ class UNetPlan:
         cfg.mfma_split = 1 if (isinstance(dtype, str) and dtype in SPLIT_DTYPES) else 0
         cfg.resblock_updown = 1 if resblock_updown else 0
         cfg.use_freq = 1 if use_freq else 0
+        cfg.additive_skips = 1 if additive_skips else 0
         self.use_freq = bool(use_freq)
         self.dtype = cfg.dtype
         self.torch_dtype = TORCH_DT[cfg.dtype]

@@ -11,7 +11,9 @@ compute dtype (``compute_dtype`` = "fp32" for reference numerics, "bf16" or
 bits); parameters stay fp32 masters and are re-packed when they change.
 
 Supported configuration family: the one run.sh uses (dims=3, no attention,
-use_scale_shift_norm=False, additive_skips=False, resample_2d=False), with
+use_scale_shift_norm=False, resample_2d=False), with the skips concatenated or,
+with additive_skips=True, averaged into the decoder (h = (h + skip) / 2 as one
+``cwdm_skip_avg`` pass per output block; run.sh's memory-saving switch), and
 either resblock_updown=True (run.sh: ResBlock down/up) or resblock_updown=False
 with conv_resample=True (Downsample = stride-2 Conv3d, Upsample = nearest x2 +
 Conv3d; unet.py:40-100).  Anything else raises NotImplementedError.
@@ -81,8 +83,6 @@ class UNetModel(nn.Module):
             unsupported.append("resblock_updown=False with conv_resample=False (parameter-free pool / nearest layers)")
         if use_scale_shift_norm:
             unsupported.append("use_scale_shift_norm=True")
-        if additive_skips:
-            unsupported.append("additive_skips=True")
         if resample_2d:
             unsupported.append("resample_2d=True")
         if num_classes is not None:
@@ -237,7 +237,8 @@ class UNetModel(nn.Module):
         if key not in self._plans:
             self._plans[key] = UNetPlan(self.in_channels, self.model_channels, self.out_channels,
                                         self.num_res_blocks, self.channel_mult, self.num_groups, dtype,
-                                        resblock_updown=self.resblock_updown, use_freq=self.use_freq)
+                                        resblock_updown=self.resblock_updown, use_freq=self.use_freq,
+                                        additive_skips=bool(self.additive_skips))
         return self._plans[key]
 
     @property

@@ -116,6 +116,20 @@ typedef struct {
 int64_t cwdm_haar_nd_parts(int64_t d, int64_t h, int64_t w);
 int cwdm_haar_nd(const cwdm_haar_nd_desc* desc, cwdm_stream_t stream);
 
+/* cwdm_skip_avg: the additive skip of UNetModel(additive_skips=True)
+ * (guided_diffusion/unet.py:793-794): out = (a + b) / 2, computed in fp32 and
+ * rounded once.  a, b, out: channels-last (B, V, C) in dtype.  stats: NULL or
+ * fp32 [B][cwdm_skip_avg_parts(V)][C][2] (sum, sum^2) of the fp32 value before
+ * rounding, one row per workgroup (a fixed contiguous voxel range), summed in a
+ * fixed order without atomics.  C: a multiple of 8, <= 2048.
+ * cwdm_skip_avg_bwd, its adjoint: da (+)= dy / 2, db (+)= dy / 2 (acc_a / acc_b:
+ * add to the existing contents). */
+int64_t cwdm_skip_avg_parts(int64_t V);
+int cwdm_skip_avg(const void* a, const void* b, void* out, float* stats, int dtype, int64_t B, int64_t V, int C,
+                  cwdm_stream_t stream);
+int cwdm_skip_avg_bwd(const void* dy, void* da, int acc_a, void* db, int acc_b, int dtype, int64_t B, int64_t V,
+                      int C, cwdm_stream_t stream);
+
 /* cwdm_prepare_batch: the i2i front end of training_losses
  * (guided_diffusion/gaussian_diffusion.py:1131-1149) in one pass -- Haar DWT of
  * the target and the three condition volumes (LLL / 3), of the noise image (no
@@ -558,7 +572,8 @@ int cwdm_adamw_device_step(float* p, const float* g, float* m, float* v, int64_t
 /* ---------------------------------------------------------------------------
  * U-Net plan: the whole UNetModel.forward (guided_diffusion/unet.py:754-800)
  * for the run.sh configuration family (no attention, resblock_updown=True,
- * use_scale_shift_norm=False, additive_skips=False, resample_2d=False, dims=3).
+ * use_scale_shift_norm=False, resample_2d=False, dims=3; skips concatenated or,
+ * with additive_skips, averaged: cwdm_skip_avg).
  * Topology and parameter names/shapes follow UNetModel.__init__
  * (unet.py:482-725) so reference state_dicts load unchanged.
  * ------------------------------------------------------------------------- */
@@ -576,6 +591,9 @@ typedef struct {
   int mfma_split;      /* fp32 plans: 1 = the accurate fast mode -- the wide-grid 3x3x3 convs run their MFMAs on
                           bf16 hi/lo splits of the fp32 operands (cwdm_conv3d_pack_split, conv3d_v5.hip); fp32
                           storage and everything else unchanged */
+  int additive_skips;  /* 1: every output block takes h = (h + skip) / 2 instead of cat([h, skip])
+                          (unet.py:661-719, :793-794); its first ResBlock maps ch -> the next skip's channels.
+                          Not with use_freq */
 } cwdm_unet_config;
 
 int cwdm_unet_create(const cwdm_unet_config* cfg, cwdm_unet** plan);
