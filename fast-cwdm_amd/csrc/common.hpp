@@ -30,24 +30,24 @@ int fail(int code, const std::string& msg);
 #define CWDM_LAUNCHED() CWDM_HIP(hipGetLastError())
 
 // ---- per-conv profiling hook (cwdm_unet_set_profiling) --------------------
-// The plan arms it around one conv call; the launch sites of the MFMA conv
-// kernels (DMA-staged, brick/wide, head) record an event pair around their own
-// launch and the algorithmic flops it covers -- so the bench's roofline times
-// exactly those kernels, not the GroupNorm pre-passes or split-K finishes.
+// The plan hands one to a conv call (ConvCall::prof, internal.hpp); the launch
+// sites of the MFMA conv kernels (DMA-staged, brick/wide, head) record an event
+// pair around their own launch and the algorithmic flops it covers -- so the
+// bench's roofline times exactly those kernels, not the GroupNorm pre-passes or
+// split-K finishes.  A null hook records nothing.
 struct ProfHook {
   hipEvent_t ev[2][2];
   double flops[2];
   int n = 0;  // brackets used (<= 2 MFMA kernels per conv call)
 };
-inline thread_local ProfHook* g_prof = nullptr;
-inline void prof_begin(hipStream_t s) {
-  if (g_prof && g_prof->n < 2) (void)hipEventRecord(g_prof->ev[g_prof->n][0], s);
+inline void prof_begin(ProfHook* h, hipStream_t s) {
+  if (h && h->n < 2) (void)hipEventRecord(h->ev[h->n][0], s);
 }
-inline void prof_end(hipStream_t s, double flops) {
-  if (g_prof && g_prof->n < 2) {
-    (void)hipEventRecord(g_prof->ev[g_prof->n][1], s);
-    g_prof->flops[g_prof->n] = flops;
-    ++g_prof->n;
+inline void prof_end(ProfHook* h, hipStream_t s, double flops) {
+  if (h && h->n < 2) {
+    (void)hipEventRecord(h->ev[h->n][1], s);
+    h->flops[h->n] = flops;
+    ++h->n;
   }
 }
 
@@ -172,9 +172,9 @@ inline FastDiv make_fastdiv(unsigned d) {
 __device__ __forceinline__ unsigned fdiv(unsigned n, const FastDiv& f) { return (__umulhi(n, f.m) + n) >> f.s; }
 
 
-// one conv weight pack of a batched launch (conv3d.hip pack_batch_run; the
-// U-Net plan collects its packs through g_pack_batch).  No implicit padding:
-// tables are compared bytewise to skip re-uploads.
+// one conv weight pack (conv3d.hip: built by the *_pack_job builders; the U-Net
+// plan collects its convs' jobs for one batched launch, pack_batch_run).  No
+// implicit padding: tables are compared bytewise to skip re-uploads.
 struct PackJob {
   const float* w;
   void* out;
@@ -186,17 +186,16 @@ struct PackJob {
 static_assert(sizeof(PackJob) == 64, "PackJob layout");
 
 // host side of the fused GroupNorm backward reduce (see V4Params::gx0): the
-// plan fills it before a dgrad conv and reads back used / nblk
+// plan offers it to a dgrad conv (ConvCall::gbwd) and reads back used / nblk
 struct GbwdFuse {
   const void* x0; const void* x1; int c0;   // the GroupNorm input (channels-last; x1: channels [c0, C))
   const float* ss; const float* mr; int groups;
   float* part; long long part_bytes;        // [B][nblk][C][2] partials out
   bool used; int nblk;
 };
-extern thread_local GbwdFuse* g_gbwd;
 
 // the U-Net plan's backward: the SiLU(GroupNorm) backward's apply pass of a
-// skip block's GN1, fused into its 1x1 skip dgrad (pointwise.hip pw_kernel):
+// skip block's GN1, fused into its 1x1 skip dgrad (ConvCall::gapply; pointwise.hip pw_kernel):
 // dx = W_skip^T dY (+ dx) + k0 SiLU'(x sc + sh) du + k1 x + k2, written once
 struct GapplyFuse {
   const void* x0; const void* x1;  // the GroupNorm input = the skip conv's input (split as the dgrad's outputs)
@@ -205,10 +204,9 @@ struct GapplyFuse {
   const float* coef;               // [B][N][4] k0, k1, k2 (gn_bwd_finalize)
   bool used;
 };
-extern thread_local GapplyFuse* g_gapply;
 
 // The U-Net plan's forward: a GroupNorm finalize (statistics partials -> scale /
-// shift, cwdm_gn_finalize) offered to the consumer conv.  Where the conv's
+// shift, cwdm_gn_finalize) offered to the consumer conv (ConvCall::gnfin).  Where the conv's
 // GroupNorm+SiLU pre-pass runs at a small grid it computes the finalize itself
 // (gn_fin_apply, conv3d_v4.hip: each workgroup reduces the partials of its 16
 // channels); any other route runs cwdm_gn_finalize first (gnfin_flush).  Either
@@ -223,5 +221,4 @@ struct GnFinFuse {
   long long B;
   bool used;
 };
-extern thread_local GnFinFuse* g_gnfin;
 }  // namespace cwdm

@@ -228,7 +228,7 @@ __global__ void __launch_bounds__(256) pack_tile_kernel(const PackJob* __restric
 // chunk's (hi(x) | lo(x)) halo planes, C = [lo(w_a) | lo(w_b)] over (hi(x_a) |
 // hi(x_b)); hi = bf16(w), lo = bf16(w - hi): hi.hi + lo.hi + hi.lo of every
 // product, fp32-accumulated.  Quad slots swizzled by bit 3 of the output row as
-// in pack_impl (only C's two quads differ).
+// in pack_elem (only C's two quads differ).
 __global__ void __launch_bounds__(256) pack_split_kernel(const float* __restrict__ w, int cout, int cin, int NT,
                                                          bf16_t* __restrict__ out, long long total) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -257,11 +257,11 @@ __global__ void __launch_bounds__(256) pack_split_kernel(const float* __restrict
 }
 
 template <typename T, int NF>
-int dispatch_brick(const ConvParams& p, const Brick& br, hipStream_t s) {
-  if (br.bx == 32 && br.bz == 4) return launch_wide<T, NF>(p, s);
-  if (br.bx == 32) return launch_conv<T, 32, 4, 2, NF>(p, s);
-  if (br.bx == 16) return launch_conv<T, 16, 4, 4, NF>(p, s);
-  return launch_conv<T, 8, 8, 4, NF>(p, s);
+int dispatch_brick(const ConvParams& p, const Brick& br, ProfHook* prof, hipStream_t s) {
+  if (br.bx == 32 && br.bz == 4) return launch_wide<T, NF>(p, prof, s);
+  if (br.bx == 32) return launch_conv<T, 32, 4, 2, NF>(p, prof, s);
+  if (br.bx == 16) return launch_conv<T, 16, 4, 4, NF>(p, prof, s);
+  return launch_conv<T, 8, 8, 4, NF>(p, prof, s);
 }
 
 // K-split factor: small grids (the U-Net's 32^3 .. 8^3 levels) get split-K so
@@ -291,8 +291,10 @@ extern "C" int64_t cwdm_conv3d_packed_bytes(int cout, int cin, int ksize, int dt
   return (int64_t)nct * (cin / ck) * ntaps * NT * ck * esz;
 }
 
-static int pack_impl(const float* w, int cout, int cin, int ksize, int dtype, void* packed, int transpose,
-                     cwdm_stream_t stream, int s2_ci0 = 0) {
+namespace cwdm {
+namespace {
+int pack_job_impl(const float* w, int cout, int cin, int ksize, int dtype, void* packed, int transpose, int s2_ci0,
+                  PackJob& j) {
   CWDM_REQUIRE(w && packed, CWDM_E_INVALID, "cwdm_conv3d_pack: null pointer");
   CWDM_REQUIRE(ksize == 1 || ksize == 3, CWDM_E_UNSUPPORTED, "cwdm_conv3d_pack: kernel size must be 1 or 3");
   CWDM_REQUIRE(dtype_compute(dtype), CWDM_E_INVALID, "cwdm_conv3d_pack: bad dtype");
@@ -305,23 +307,64 @@ static int pack_impl(const float* w, int cout, int cin, int ksize, int dtype, vo
   const int nct = (int)ceil_div(cout, NT);
   const int ntaps = ksize * ksize * ksize;
   const long long total = (long long)nct * (cin / ck) * ntaps * NT * ck;
-  if (g_pack_batch) {  // the U-Net plan collects its packs and launches them together (pack_batch_run)
-    g_pack_batch->push_back(PackJob{w, packed, total, cout, cin, ntaps, NT, transpose, cin_real, s2_ci0, 0, 0});
-    return CWDM_OK;
-  }
-  dim3 grid((unsigned)ceil_div(total, 256));
+  j = PackJob{w, packed, total, cout, cin, ntaps, NT, transpose, cin_real, s2_ci0, 0, 0};
+  return CWDM_OK;
+}
+
+// one job on its own (the public packs)
+int pack_launch(const PackJob& j, int dtype, cwdm_stream_t stream) {
+  const dim3 grid((unsigned)ceil_div(j.total, 256));
   return dispatch_dtype(dtype, [&](auto tag) -> int {
     using T = decltype(tag);
-    hipLaunchKernelGGL(pack_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, w, cout, cin, ntaps, NT, nct,
-                       reinterpret_cast<T*>(packed), transpose, cin_real, s2_ci0);
+    T* out = reinterpret_cast<T*>(j.out);
+    if constexpr (sizeof(T) == 2) {
+      if (j.phase) {
+        hipLaunchKernelGGL(pack_phase_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, j.w, j.cout, j.cin, out,
+                           j.total);
+        CWDM_LAUNCHED();
+        return CWDM_OK;
+      }
+    }
+    hipLaunchKernelGGL(pack_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, j.w, j.cout, j.cin, j.ntaps, j.NT,
+                       (int)ceil_div(j.cout, j.NT), out, j.transpose, j.cin_real, j.s2_ci0);
     CWDM_LAUNCHED();
     return CWDM_OK;
   });
 }
+}  // namespace
+
+int pack_job(const float* w, int cout, int cin, int ksize, int dtype, void* packed, PackJob& j) {
+  return pack_job_impl(w, cout, cin, ksize, dtype, packed, 0, 0, j);
+}
+
+int pack_s2_job(const float* w, int cout, int cin, int dtype, void* packed, int transpose, PackJob& j) {
+  // forward: a (cout -> 8 cin) conv over the space-to-depth input; transpose: its dgrad (8 cin outputs)
+  return transpose ? pack_job_impl(w, 8 * cin, cout, 3, dtype, packed, 1, cin, j)
+                   : pack_job_impl(w, cout, 8 * cin, 3, dtype, packed, 0, cin, j);
+}
+
+int pack_dgrad_job(const float* w, int cout, int cin, int ksize, int dtype, void* packed, PackJob& j) {
+  // the dgrad conv maps cout channels back to cin: packed as a (cout -> cin) conv
+  // (its input channels are padded with zeros up to the chunk size, e.g. the
+  // 8-channel output head)
+  return pack_job_impl(w, cin, cout, ksize, dtype, packed, 1, 0, j);
+}
+
+int pack_phase_job(const float* w, int cout, int cin, int dtype, void* packed, PackJob& j) {
+  CWDM_REQUIRE(w && packed, CWDM_E_INVALID, "cwdm_conv3d_pack_phase: null pointer");
+  CWDM_REQUIRE(dtype_half(dtype) && cout > 0 && cout % 64 == 0 && cin > 0 && cin % 16 == 0, CWDM_E_UNSUPPORTED,
+               "cwdm_conv3d_pack_phase: bf16 / fp16, cout % 64 == 0, cin % 16 == 0");
+  const long long total = cwdm_conv3d_packed_phase_bytes(cout, cin, dtype) / 2;
+  j = PackJob{w, packed, total, cout, cin, 8, 64, 0, cin, 0, 1, 0};
+  return CWDM_OK;
+}
+}  // namespace cwdm
 
 extern "C" int cwdm_conv3d_pack(const float* w, int cout, int cin, int ksize, int dtype, void* packed,
                                 cwdm_stream_t stream) {
-  return pack_impl(w, cout, cin, ksize, dtype, packed, 0, stream);
+  PackJob j;
+  if (int rc = pack_job(w, cout, cin, ksize, dtype, packed, j)) return rc;
+  return pack_launch(j, dtype, stream);
 }
 
 extern "C" int64_t cwdm_conv3d_packed_split_bytes(int cout, int cin) {
@@ -348,43 +391,26 @@ extern "C" int64_t cwdm_conv3d_packed_phase_bytes(int cout, int cin, int dtype) 
 
 extern "C" int cwdm_conv3d_pack_phase(const float* w, int cout, int cin, int dtype, void* packed,
                                       cwdm_stream_t stream) {
-  CWDM_REQUIRE(w && packed, CWDM_E_INVALID, "cwdm_conv3d_pack_phase: null pointer");
-  CWDM_REQUIRE(dtype_half(dtype) && cout > 0 && cout % 64 == 0 && cin > 0 && cin % 16 == 0, CWDM_E_UNSUPPORTED,
-               "cwdm_conv3d_pack_phase: bf16 / fp16, cout % 64 == 0, cin % 16 == 0");
-  const long long total = cwdm_conv3d_packed_phase_bytes(cout, cin, dtype) / 2;
-  if (g_pack_batch) {  // joins the U-Net plan's batched pack (pack_batch_run)
-    g_pack_batch->push_back(PackJob{w, packed, total, cout, cin, 8, 64, 0, cin, 0, 1, 0});
-    return CWDM_OK;
-  }
-  const dim3 grid((unsigned)ceil_div(total, 256));
-  if (dtype == CWDM_BF16)
-    hipLaunchKernelGGL(pack_phase_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, w, cout, cin,
-                       reinterpret_cast<bf16_t*>(packed), total);
-  else
-    hipLaunchKernelGGL(pack_phase_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, w, cout, cin,
-                       reinterpret_cast<f16_t*>(packed), total);
-  CWDM_LAUNCHED();
-  return CWDM_OK;
+  PackJob j;
+  if (int rc = pack_phase_job(w, cout, cin, dtype, packed, j)) return rc;
+  return pack_launch(j, dtype, stream);
 }
 
 extern "C" int cwdm_conv3d_pack_s2(const float* w, int cout, int cin, int dtype, void* packed, int transpose,
                                    cwdm_stream_t stream) {
-  // forward: a (cout -> 8 cin) conv over the space-to-depth input; transpose: its dgrad (8 cin outputs)
-  return transpose ? pack_impl(w, 8 * cin, cout, 3, dtype, packed, 1, stream, cin)
-                   : pack_impl(w, cout, 8 * cin, 3, dtype, packed, 0, stream, cin);
+  PackJob j;
+  if (int rc = pack_s2_job(w, cout, cin, dtype, packed, transpose, j)) return rc;
+  return pack_launch(j, dtype, stream);
 }
 
 extern "C" int cwdm_conv3d_pack_dgrad(const float* w, int cout, int cin, int ksize, int dtype, void* packed,
                                       cwdm_stream_t stream) {
-  // the dgrad conv maps cout channels back to cin: packed as a (cout -> cin) conv
-  // (its input channels are padded with zeros up to the chunk size, e.g. the
-  // 8-channel output head)
-  return pack_impl(w, cin, cout, ksize, dtype, packed, 1, stream);
+  PackJob j;
+  if (int rc = pack_dgrad_job(w, cout, cin, ksize, dtype, packed, j)) return rc;
+  return pack_launch(j, dtype, stream);
 }
 
 namespace cwdm {
-thread_local std::vector<PackJob>* g_pack_batch = nullptr;
-
 // one launch for the collected packs; the job table goes to `table` (device,
 // >= jobs.size() entries), uploaded only when it differs from `cache`
 int pack_batch_run(std::vector<PackJob>& jobs, int dtype, PackJob* table, std::vector<PackJob>& cache,
@@ -451,7 +477,9 @@ Plan1 plan_conv(const cwdm_conv3d_desc* d) {
 extern "C" int64_t cwdm_conv3d_workspace_bytes(const cwdm_conv3d_desc* d) {
   if (!d || d->B <= 0 || d->D <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0) return -1;
   const int64_t legacy = plan_conv(d).ws;
-  return (v4_eligible(d) || (d->a_w_split && v5_eligible(d, false))) ? std::max(legacy, v4_workspace_bytes(d)) : legacy;
+  const ConvCall c;
+  return (v4_eligible(d, c) || (d->a_w_split && v5_eligible(d, false, c))) ? std::max(legacy, v4_workspace_bytes(d, c))
+                                                                           : legacy;
 }
 
 extern "C" int64_t cwdm_conv3d_parts(int dtype, int64_t D, int64_t H, int64_t W, int cout) {
@@ -460,7 +488,28 @@ extern "C" int64_t cwdm_conv3d_parts(int dtype, int64_t D, int64_t H, int64_t W,
   return ceil_div(D, br.bz) * ceil_div(H, br.by) * ceil_div(W, br.bx);
 }
 
+// the state behind cwdm_debug_stats_wg, per calling thread: the layout asked of lone
+// cwdm_conv3d_forward calls, and the rows the last of them wrote that way
+static thread_local int t_stats_wg = 0;
+static thread_local int64_t t_stats_rows = 0;
+
+extern "C" int64_t cwdm_debug_stats_wg(int on) {
+  if (on < 0) return t_stats_rows;
+  const int prev = t_stats_wg;
+  t_stats_wg = on ? 1 : 0;
+  t_stats_rows = 0;
+  return prev;
+}
+
 extern "C" int cwdm_conv3d_forward(const cwdm_conv3d_desc* d, cwdm_stream_t stream) {
+  ConvCall c;
+  c.stats_wg = t_stats_wg != 0;
+  const int rc = conv3d_forward(d, c, (hipStream_t)stream);
+  if (c.stats_rows > 0) t_stats_rows = c.stats_rows;
+  return rc;
+}
+
+int cwdm::conv3d_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s) {
   CWDM_REQUIRE(d && d->out && (d->a_w || d->b_w), CWDM_E_INVALID, "cwdm_conv3d_forward: null pointer");
   CWDM_REQUIRE(!d->a_w || (d->a0 && d->a_c0 > 0), CWDM_E_INVALID, "cwdm_conv3d_forward: segment A input missing");
   CWDM_REQUIRE(dtype_compute(d->dtype), CWDM_E_INVALID, "cwdm_conv3d_forward: bad dtype");
@@ -484,24 +533,24 @@ extern "C" int cwdm_conv3d_forward(const cwdm_conv3d_desc* d, cwdm_stream_t stre
   // DMA-staged one, whose pre-pass may take it)
   int rc;
   if (head_eligible(d)) {
-    if ((rc = gnfin_flush(d, (hipStream_t)stream))) return rc;
-    return head_conv_forward(d, (hipStream_t)stream);
+    if ((rc = gnfin_flush(d, c.gnfin, s))) return rc;
+    return head_conv_forward(d, c.prof, s);
   }
   if (pw_eligible(d)) {
-    if ((rc = gnfin_flush(d, (hipStream_t)stream))) return rc;
-    return pw_forward(d, (hipStream_t)stream);
+    if ((rc = gnfin_flush(d, c.gnfin, s))) return rc;
+    return pw_forward(d, c, s);
   }
   // (the accurate fast mode's split-bf16 kernel takes fp32 shapes of any size: the same host path)
-  if (v4_eligible(d) || (d->a_w_split && v5_eligible(d, false))) {
-    const int64_t need = v4_workspace_bytes(d);
-    if (need == 0 || (d->workspace && d->ws_bytes >= need)) return conv3d_v4_forward(d, (hipStream_t)stream);
+  if (v4_eligible(d, c) || (d->a_w_split && v5_eligible(d, false, c))) {
+    const int64_t need = v4_workspace_bytes(d, c);
+    if (need == 0 || (d->workspace && d->ws_bytes >= need)) return conv3d_v4_forward(d, c, s);
   }
-  if ((rc = gnfin_flush(d, (hipStream_t)stream))) return rc;
-  return legacy_conv3d_forward(d, stream);
+  if ((rc = gnfin_flush(d, c.gnfin, s))) return rc;
+  return legacy_conv3d_forward(d, c.prof, s);
 }
 
 // the brick / split-K kernels of conv3d_kernels.hpp (every shape and mode)
-int cwdm::legacy_conv3d_forward(const cwdm_conv3d_desc* d, cwdm_stream_t stream) {
+int cwdm::legacy_conv3d_forward(const cwdm_conv3d_desc* d, ProfHook* prof, hipStream_t s) {
   const Plan1 pl = plan_conv(d);
   const int nf = pl.nf;
   CWDM_REQUIRE(nf == 2 || d->cout % 32 == 0 || d->cout < 32, CWDM_E_UNSUPPORTED,
@@ -530,10 +579,9 @@ int cwdm::legacy_conv3d_forward(const cwdm_conv3d_desc* d, cwdm_stream_t stream)
     p.ksplit = pl.S;
     p.partial = reinterpret_cast<float*>(d->workspace);
   }
-  hipStream_t s = (hipStream_t)stream;
   return dispatch_dtype(d->dtype, [&](auto tag) -> int {
     using T = decltype(tag);
-    return nf == 2 ? dispatch_brick<T, 2>(p, br, s) : dispatch_brick<T, 1>(p, br, s);
+    return nf == 2 ? dispatch_brick<T, 2>(p, br, prof, s) : dispatch_brick<T, 1>(p, br, prof, s);
   });
 }
 

@@ -697,7 +697,7 @@ int head2_launch(HeadParams p, hipStream_t s) {
 }
 }  // namespace
 
-int head_conv_forward(const cwdm_conv3d_desc* d, hipStream_t s) {
+int head_conv_forward(const cwdm_conv3d_desc* d, ProfHook* prof, hipStream_t s) {
   HeadParams p{};
   p.B = (int)d->B; p.D = (int)d->D; p.H = (int)d->H; p.W = (int)d->W; p.C = d->a_c0; p.cout = d->cout;
   p.tx = p.W / 32; p.ty = p.H / 4; p.tz = p.D / 4;
@@ -708,7 +708,7 @@ int head_conv_forward(const cwdm_conv3d_desc* d, hipStream_t s) {
   p.out = d->out; p.out_f32 = d->out_dtype == CWDM_F32;
   const long long nblk = (long long)p.B * p.tx * p.ty * p.tz;
   CWDM_REQUIRE(nblk < (1LL << 31), CWDM_E_UNSUPPORTED, "conv3d head: grid too large");
-  prof_begin(s);
+  prof_begin(prof, s);
   const dim3 grid((unsigned)nblk);
   if (head2_ok(d)) {
     int rc;
@@ -722,7 +722,7 @@ int head_conv_forward(const cwdm_conv3d_desc* d, hipStream_t s) {
     if (p.gn) hipLaunchKernelGGL((head_conv_kernel<bf16_t, true>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((head_conv_kernel<bf16_t, false>), grid, dim3(256), 0, s, p);
   }
-  prof_end(s, 2.0 * p.B * p.D * p.H * p.W * (double)p.cout * 27.0 * p.C);
+  prof_end(prof, s, 2.0 * p.B * p.D * p.H * p.W * (double)p.cout * 27.0 * p.C);
   CWDM_LAUNCHED();
   return CWDM_OK;
 }
@@ -735,7 +735,7 @@ bool head_sampler_eligible(const cwdm_conv3d_desc* d, const cwdm_sampler_args* a
          (!a->mirror || a->mirror_dtype == d->dtype || a->mirror_dtype == CWDM_F32);
 }
 
-int head_sampler_forward(const cwdm_conv3d_desc* d, const cwdm_sampler_args* a, hipStream_t s) {
+int head_sampler_forward(const cwdm_conv3d_desc* d, const cwdm_sampler_args* a, ProfHook* prof, hipStream_t s) {
   HeadParams p{};
   p.B = (int)d->B; p.D = (int)d->D; p.H = (int)d->H; p.W = (int)d->W; p.C = d->a_c0; p.cout = d->cout;
   p.tx = p.W / 32; p.ty = p.H / 4; p.tz = p.D / 4;
@@ -750,7 +750,7 @@ int head_sampler_forward(const cwdm_conv3d_desc* d, const cwdm_sampler_args* a, 
   const long long nblk = (long long)p.B * p.tx * p.ty * p.tz;
   CWDM_REQUIRE(nblk < (1LL << 31), CWDM_E_UNSUPPORTED, "conv3d head: grid too large");
   const bool f32m = a->mirror && a->mirror_dtype == CWDM_F32;
-  prof_begin(s);
+  prof_begin(prof, s);
   if (head2_ok(d)) {
     int rc;
     if (d->dtype == CWDM_F16)
@@ -765,7 +765,7 @@ int head_sampler_forward(const cwdm_conv3d_desc* d, const cwdm_sampler_args* a, 
     if (f32m) hipLaunchKernelGGL((head_conv_kernel<bf16_t, true, true, float>), dim3((unsigned)nblk), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((head_conv_kernel<bf16_t, true, true, bf16_t>), dim3((unsigned)nblk), dim3(256), 0, s, p);
   }
-  prof_end(s, 2.0 * p.B * p.D * p.H * p.W * (double)p.cout * 27.0 * p.C);
+  prof_end(prof, s, 2.0 * p.B * p.D * p.H * p.W * (double)p.cout * 27.0 * p.C);
   CWDM_LAUNCHED();
   return CWDM_OK;
 }

@@ -1024,12 +1024,12 @@ inline double conv_flops(const ConvParams& p) {
 }
 
 template <typename T, int BX, int BY, int BZ, int NF>
-int launch_conv(const ConvParams& p, hipStream_t s) {
+int launch_conv(const ConvParams& p, ProfHook* prof, hipStream_t s) {
   const long long nblk = (long long)p.B * p.tx * p.ty * p.tz * p.nct;
   CWDM_REQUIRE(nblk * p.ksplit < (1LL << 31), CWDM_E_UNSUPPORTED, "conv3d: grid too large");
   const dim3 grid((unsigned)(nblk * p.ksplit));
   const bool gn = p.agn != nullptr;
-  prof_begin(s);
+  prof_begin(prof, s);
   if (p.amode == 0) {
     if (gn) hipLaunchKernelGGL((conv3d_kernel<T, BX, BY, BZ, NF, 0, true>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((conv3d_kernel<T, BX, BY, BZ, NF, 0, false>), grid, dim3(256), 0, s, p);
@@ -1040,7 +1040,7 @@ int launch_conv(const ConvParams& p, hipStream_t s) {
     if (gn) hipLaunchKernelGGL((conv3d_kernel<T, BX, BY, BZ, NF, 2, true>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((conv3d_kernel<T, BX, BY, BZ, NF, 2, false>), grid, dim3(256), 0, s, p);
   }
-  prof_end(s, conv_flops(p));
+  prof_end(prof, s, conv_flops(p));
   CWDM_LAUNCHED();
   if (p.ksplit > 1) {
     const long long n4 = (long long)p.B * p.D * p.H * p.W * p.cout / 4;
@@ -1055,12 +1055,12 @@ int launch_conv(const ConvParams& p, hipStream_t s) {
 }
 
 template <typename T, int NF>
-int launch_wide(const ConvParams& p, hipStream_t s) {
+int launch_wide(const ConvParams& p, ProfHook* prof, hipStream_t s) {
   const long long nblk = (long long)p.B * p.tx * p.ty * p.tz * p.nct;
   CWDM_REQUIRE(nblk * p.ksplit < (1LL << 31), CWDM_E_UNSUPPORTED, "conv3d: grid too large");
   const dim3 grid((unsigned)(nblk * p.ksplit));
   const bool gn = p.agn != nullptr;
-  prof_begin(s);
+  prof_begin(prof, s);
   if (p.amode == 0) {
     if (gn) hipLaunchKernelGGL((conv3d_wide_kernel<T, NF, 0, true>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((conv3d_wide_kernel<T, NF, 0, false>), grid, dim3(256), 0, s, p);
@@ -1071,7 +1071,7 @@ int launch_wide(const ConvParams& p, hipStream_t s) {
     if (gn) hipLaunchKernelGGL((conv3d_wide_kernel<T, NF, 2, true>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((conv3d_wide_kernel<T, NF, 2, false>), grid, dim3(256), 0, s, p);
   }
-  prof_end(s, conv_flops(p));
+  prof_end(prof, s, conv_flops(p));
   CWDM_LAUNCHED();
   if (p.ksplit > 1) {
     const long long n4 = (long long)p.B * p.D * p.H * p.W * p.cout / 4;
@@ -1088,15 +1088,15 @@ int launch_wide(const ConvParams& p, hipStream_t s) {
 // The explicit instances of launch_wide / launch_conv, listed once: conv3d.hip
 // declares them (KW = extern template) and the conv3d_inst_{wide,small}_<dtype>.hip
 // units, split for compile time, define them (KW = template).
-#define CWDM_WIDE_INSTANCES(KW, T)                                \
-  KW int launch_wide<T, 1>(const ConvParams&, hipStream_t);       \
-  KW int launch_wide<T, 2>(const ConvParams&, hipStream_t);
-#define CWDM_SMALL_INSTANCES(KW, T)                                     \
-  KW int launch_conv<T, 32, 4, 2, 1>(const ConvParams&, hipStream_t);   \
-  KW int launch_conv<T, 16, 4, 4, 1>(const ConvParams&, hipStream_t);   \
-  KW int launch_conv<T, 8, 8, 4, 1>(const ConvParams&, hipStream_t);    \
-  KW int launch_conv<T, 32, 4, 2, 2>(const ConvParams&, hipStream_t);   \
-  KW int launch_conv<T, 16, 4, 4, 2>(const ConvParams&, hipStream_t);   \
-  KW int launch_conv<T, 8, 8, 4, 2>(const ConvParams&, hipStream_t);
+#define CWDM_WIDE_INSTANCES(KW, T)                                           \
+  KW int launch_wide<T, 1>(const ConvParams&, ProfHook*, hipStream_t);       \
+  KW int launch_wide<T, 2>(const ConvParams&, ProfHook*, hipStream_t);
+#define CWDM_SMALL_INSTANCES(KW, T)                                                \
+  KW int launch_conv<T, 32, 4, 2, 1>(const ConvParams&, ProfHook*, hipStream_t);   \
+  KW int launch_conv<T, 16, 4, 4, 1>(const ConvParams&, ProfHook*, hipStream_t);   \
+  KW int launch_conv<T, 8, 8, 4, 1>(const ConvParams&, ProfHook*, hipStream_t);    \
+  KW int launch_conv<T, 32, 4, 2, 2>(const ConvParams&, ProfHook*, hipStream_t);   \
+  KW int launch_conv<T, 16, 4, 4, 2>(const ConvParams&, ProfHook*, hipStream_t);   \
+  KW int launch_conv<T, 8, 8, 4, 2>(const ConvParams&, ProfHook*, hipStream_t);
 
 }  // namespace cwdm

@@ -97,9 +97,6 @@ struct SGParams {
 #define SG_DIAG(bit) false
 #endif
 
-// counter block pre-zeroed by the caller (the U-Net plan, per forward /
-// backward, thread-local for the duration of its launch list) or null
-thread_local unsigned* g_sg_sync = nullptr;
 constexpr int64_t kSgSyncWords = 1 << 16;   // tiles of one K-split launch (sg_split_for keeps tiles * S below)
 
 __device__ __forceinline__ void sg_mfma(sg_f32x4& acc, const u32x4& a, const u32x4& b, bf16_t*) {
@@ -449,15 +446,13 @@ template __global__ void conv3d_sg_kernel<f16_t, 8, 8, 0, 27>(SGParams);
 template __global__ void conv3d_sg_kernel<f16_t, 8, 8, 1, 27>(SGParams);
 template __global__ void conv3d_sg_kernel<f16_t, 8, 8, 0, 1>(SGParams);
 
-// set by the U-Net plan around the accurate fast mode's K-expanded small-grid convs: a 16-bit conv
-// with fp32 output takes this kernel, its residual fp32 too (SgFp32xScope)
-thread_local bool g_sg_fp32x = false;
-
+// fp32x (ConvCall::fp32x, set by the U-Net plan for the accurate fast mode's K-expanded small-grid
+// convs): a 16-bit conv with fp32 output takes this kernel, its residual fp32 too
 namespace {
-bool sg_shape_ok(const cwdm_conv3d_desc* d) {
+bool sg_shape_ok(const cwdm_conv3d_desc* d, bool fp32x) {
   if (g_conv_path.load(std::memory_order_relaxed) == 1) return false;
   if (!dtype_half(d->dtype) || d->accumulate || d->out1 || d->cout % 64) return false;
-  if (d->out_dtype != d->dtype && !(d->out_dtype == CWDM_F32 && g_sg_fp32x)) return false;
+  if (d->out_dtype != d->dtype && !(d->out_dtype == CWDM_F32 && fp32x)) return false;
   // W < kWideMinW (the wide kernels take the rest): 16 x 4 x 4 bricks for W >= 16,
   // 8 x 8 x 4 below (pick_brick's statistics bricks), the last brick of an axis partial
   return d->W >= 1 && d->W < kWideMinW && d->H >= 1 && d->D >= 1;
@@ -476,8 +471,8 @@ SgGeom sg_geom(const cwdm_conv3d_desc* d) {
 // (16x4x4 statistics bricks) or W = 8 (8x8x4), 32-channel K chunks.  At 8^3
 // there are only 32 tiles: K split across workgroups (sg_ksplit), finished by
 // the last slice of each tile.
-bool sg_eligible(const cwdm_conv3d_desc* d) {
-  if (!sg_shape_ok(d) || !d->a_w) return false;
+bool sg_eligible(const cwdm_conv3d_desc* d, bool fp32x) {
+  if (!sg_shape_ok(d, fp32x) || !d->a_w) return false;
   if (d->a_mode != 0 && d->a_mode != 1) return false;
   if (d->res_mode < -1 || d->res_mode > 1) return false;
   if ((d->a_c0 + d->a_c1) % 32 || d->a_c0 % 16) return false;
@@ -487,8 +482,8 @@ bool sg_eligible(const cwdm_conv3d_desc* d) {
 }
 
 // the 1x1 skip segment alone (segment B of a desc, channels-last sources)
-bool sg_skip_eligible(const cwdm_conv3d_desc* d) {
-  if (!sg_shape_ok(d) || !d->b_w) return false;
+bool sg_skip_eligible(const cwdm_conv3d_desc* d, bool fp32x) {
+  if (!sg_shape_ok(d, fp32x) || !d->b_w) return false;
   if ((d->b_c0 + d->b_c1) % 32 || d->b_c0 % 16) return false;
   const int64_t V = d->D * d->H * d->W;
   return V * (d->b_c0 + d->b_c1) * 2 < 0xFFFFE000LL && d->B * (V / 256) * (d->cout / 16) < (1LL << 31);
@@ -516,31 +511,35 @@ int sg_split_for(const cwdm_conv3d_desc* d, int cin, bool skip = false) {
 }
 }  // namespace
 
-int sg_ksplit(const cwdm_conv3d_desc* d) { return sg_eligible(d) ? sg_split_for(d, d->a_c0 + d->a_c1) : 1; }
+int sg_ksplit(const cwdm_conv3d_desc* d, bool fp32x) {
+  return sg_eligible(d, fp32x) ? sg_split_for(d, d->a_c0 + d->a_c1) : 1;
+}
 // voxels per batch of one K-split slice: the small-grid kernel stores whole
 // (possibly partial) bricks of 256 voxels, the wide kernel the grid itself
-int64_t ksplit_slice_voxels(const cwdm_conv3d_desc* d) {
-  return sg_shape_ok(d) ? sg_geom(d).parts() * 256 : d->D * d->H * d->W;
+int64_t ksplit_slice_voxels(const cwdm_conv3d_desc* d, bool fp32x) {
+  return sg_shape_ok(d, fp32x) ? sg_geom(d).parts() * 256 : d->D * d->H * d->W;
 }
-int sg_skip_ksplit(const cwdm_conv3d_desc* d) { return sg_skip_eligible(d) ? sg_split_for(d, d->b_c0 + d->b_c1, true) : 1; }
+int sg_skip_ksplit(const cwdm_conv3d_desc* d, bool fp32x) {
+  return sg_skip_eligible(d, fp32x) ? sg_split_for(d, d->b_c0 + d->b_c1, true) : 1;
+}
 
 // bytes of the K-split counter block a lone launch keeps behind its slices (0 without a split)
 int64_t sg_sync_bytes(int ksplit) { return ksplit > 1 ? kSgSyncWords * 4 : 0; }
-// the U-Net plan's zeroed sync block: the small-grid K-split counters, then the
-// warp-specialised conv's apply-ahead sweep counters (kV5AaWords)
+// a caller's zeroed sync block (ConvCall::sync; the U-Net plan's, per forward / backward): the
+// small-grid K-split counters, then the warp-specialised conv's apply-ahead sweep counters (kV5AaWords)
 int64_t plan_sync_bytes() { return kSgSyncWords * 4 + kV5AaWords * 4; }
-unsigned* plan_aa_counters() { return g_sg_sync ? g_sg_sync + kSgSyncWords : nullptr; }
+unsigned* plan_aa_counters(unsigned* sync) { return sync ? sync + kSgSyncWords : nullptr; }
 
 namespace {
-// counters of a K-split launch: the plan's pre-zeroed block, else `own` (the
-// workspace tail behind the slices), zeroed here by a memset node
-int sg_counters(SGParams& q, void* own, hipStream_t s) {
+// counters of a K-split launch: the caller's pre-zeroed block `sync`, else `own`
+// (the workspace tail behind the slices), zeroed here by a memset node
+int sg_counters(SGParams& q, unsigned* sync, void* own, hipStream_t s) {
   q.count = nullptr;
   if (q.ksplit == 1) return CWDM_OK;
   const int64_t tiles = (int64_t)q.v.B * q.parts * q.ntile16;
   CWDM_REQUIRE(tiles <= kSgSyncWords, CWDM_E_UNSUPPORTED, "conv3d (small grid): too many K-split tiles");
-  if (g_sg_sync) {
-    q.count = g_sg_sync;
+  if (sync) {
+    q.count = sync;
     return CWDM_OK;
   }
   CWDM_REQUIRE(own, CWDM_E_INVALID, "conv3d (small grid): K-split counters missing");
@@ -567,7 +566,7 @@ void sg_go_t(const SGParams& q, const cwdm_conv3d_desc* d, int taps, hipStream_t
   }
 }
 
-int sg_go(const SGParams& q0, const cwdm_conv3d_desc* d, int taps, double flops, hipStream_t s) {
+int sg_go(const SGParams& q0, const cwdm_conv3d_desc* d, int taps, double flops, ProfHook* prof, hipStream_t s) {
   static const int xcd_map = env_not0("CWDM_SG_XCD");
   SGParams q = q0;
   q.xcd = xcd_map;
@@ -579,39 +578,39 @@ int sg_go(const SGParams& q0, const cwdm_conv3d_desc* d, int taps, double flops,
   static const int diag = env_int("CWDM_SG_DIAGMASK", 0);
   q.diag = diag;
 #endif
-  prof_begin(s);
+  prof_begin(prof, s);
   if (d->dtype == CWDM_F16) sg_go_t<f16_t>(q, d, taps, s);
   else sg_go_t<bf16_t>(q, d, taps, s);
-  prof_end(s, flops);
+  prof_end(prof, s, flops);
   CWDM_LAUNCHED();
   return CWDM_OK;
 }
 }  // namespace
 
-// partial: fp32 scratch of sg_ksplit(d) x B x V x cout (the K-split slices) followed
+// partial: fp32 scratch of sg_ksplit(d, c.fp32x) x B x V x cout (the K-split slices) followed
 // by sg_sync_bytes of counters, else unused
-int sg_launch(const V4Params& v, const cwdm_conv3d_desc* d, void* partial, hipStream_t s) {
+int sg_launch(const V4Params& v, const cwdm_conv3d_desc* d, void* partial, const ConvCall& c, hipStream_t s) {
   SGParams q{};
   q.v = v;
   q.ntile16 = d->cout / 16;
   const SgGeom gm = sg_geom(d);
   q.parts = (int)gm.parts();
   q.tx = gm.tx; q.ty = gm.ty;
-  q.ksplit = sg_ksplit(d);
+  q.ksplit = sg_ksplit(d, c.fp32x);
   q.kper = ((d->a_c0 + d->a_c1) / 32 + q.ksplit - 1) / q.ksplit;
   q.part = reinterpret_cast<float*>(partial);
   CWDM_REQUIRE(q.ksplit == 1 || partial, CWDM_E_INVALID, "conv3d (small grid): K-split scratch missing");
   int rc;
-  if ((rc = sg_counters(q, q.ksplit > 1 ? reinterpret_cast<unsigned char*>(partial) +
-                                              (int64_t)q.ksplit * d->B * ksplit_slice_voxels(d) * d->cout * 4
-                                        : nullptr, s)))
+  if ((rc = sg_counters(q, c.sync, q.ksplit > 1 ? reinterpret_cast<unsigned char*>(partial) +
+                                                      (int64_t)q.ksplit * d->B * ksplit_slice_voxels(d, c.fp32x) * d->cout * 4
+                                                : nullptr, s)))
     return rc;
-  return sg_go(q, d, 27, 2.0 * d->B * d->D * d->H * d->W * (double)d->cout * 27.0 * (d->a_c0 + d->a_c1), s);
+  return sg_go(q, d, 27, 2.0 * d->B * d->D * d->H * d->W * (double)d->cout * 27.0 * (d->a_c0 + d->a_c1), c.prof, s);
 }
 
 // out = W_skip . [b0 | b1] (bf16, no bias / residual / statistics): the skip
-// pre-pass of conv3d_v4_forward; partial: fp32 scratch of sg_skip_ksplit(d) x B x V x cout
-int sg_skip_launch(const cwdm_conv3d_desc* d, void* out, void* partial, hipStream_t s) {
+// pre-pass of conv3d_v4_forward; partial: fp32 scratch of sg_skip_ksplit(d, c.fp32x) x B x V x cout
+int sg_skip_launch(const cwdm_conv3d_desc* d, void* out, void* partial, const ConvCall& c, hipStream_t s) {
   SGParams q{};
   V4Params& p = q.v;
   const int64_t V = d->D * d->H * d->W;
@@ -630,16 +629,16 @@ int sg_skip_launch(const cwdm_conv3d_desc* d, void* out, void* partial, hipStrea
   const SgGeom gm = sg_geom(d);
   q.parts = (int)gm.parts();
   q.tx = gm.tx; q.ty = gm.ty;
-  q.ksplit = sg_skip_ksplit(d);
+  q.ksplit = sg_skip_ksplit(d, c.fp32x);
   q.kper = ((d->b_c0 + d->b_c1) / 32 + q.ksplit - 1) / q.ksplit;
   q.part = reinterpret_cast<float*>(partial);
   CWDM_REQUIRE(q.ksplit == 1 || partial, CWDM_E_INVALID, "conv3d (small grid): K-split scratch missing");
   int rc;
-  if ((rc = sg_counters(q, q.ksplit > 1 ? reinterpret_cast<unsigned char*>(partial) +
-                                              (int64_t)q.ksplit * d->B * ksplit_slice_voxels(d) * d->cout * 4
-                                        : nullptr, s)))
+  if ((rc = sg_counters(q, c.sync, q.ksplit > 1 ? reinterpret_cast<unsigned char*>(partial) +
+                                                      (int64_t)q.ksplit * d->B * ksplit_slice_voxels(d, c.fp32x) * d->cout * 4
+                                                : nullptr, s)))
     return rc;
-  return sg_go(q, d, 1, 2.0 * d->B * V * (double)d->cout * (d->b_c0 + d->b_c1), s);
+  return sg_go(q, d, 1, 2.0 * d->B * V * (double)d->cout * (d->b_c0 + d->b_c1), c.prof, s);
 }
 
 }  // namespace cwdm

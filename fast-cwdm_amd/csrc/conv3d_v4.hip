@@ -216,8 +216,8 @@ int64_t v4_ksplit_target() {
 
 // K split of a grid with fewer tiles than two workgroups per CU (the 32^3
 // level): enough K slices for ~512 work items, at least two chunks per slice
-int v4_ksplit(const cwdm_conv3d_desc* d) {
-  if (sg_eligible(d)) return sg_ksplit(d);  // the small-grid kernel's own K split (8^3 level)
+int v4_ksplit(const cwdm_conv3d_desc* d, const ConvCall& c) {
+  if (sg_eligible(d, c.fp32x)) return sg_ksplit(d, c.fp32x);  // the small-grid kernel's own K split (8^3 level)
   const int ck = ck_of(d->dtype);
   const int nch = (d->a_c0 + d->a_c1) / ck;
   const int64_t nblk = v4_items(d);
@@ -232,12 +232,12 @@ int v4_ksplit(const cwdm_conv3d_desc* d) {
   return (nch + per - 1) / per;
 }
 
-bool v4_eligible(const cwdm_conv3d_desc* d) {
+bool v4_eligible(const cwdm_conv3d_desc* d, const ConvCall& c) {
   const int path = g_conv_path.load(std::memory_order_relaxed);
   if (path == 1) return false;
   // the 1x1 skip product is added through the residual slot: not both
   if (d->b_w && d->res_mode >= 0) return false;
-  if (sg_eligible(d)) return true;  // 16^3 / 8^3 levels: conv3d_sg.hip behind the same pre-passes
+  if (sg_eligible(d, c.fp32x)) return true;  // 16^3 / 8^3 levels: conv3d_sg.hip behind the same pre-passes
   if (!dtype_compute(d->dtype)) return false;
   // W >= kWideMinW: the statistics partials follow cwdm_conv3d_parts' 32-wide x tiles (pick_brick)
   if (!d->a_w || d->W < kWideMinW || d->H % 4 || d->D % 4 || d->cout % 64) return false;
@@ -246,7 +246,7 @@ bool v4_eligible(const cwdm_conv3d_desc* d) {
   if (d->out1 && d->out_c0 % 8) return false;
   const int64_t nblk = v4_items(d);
   // work items: K slices, or (16-bit, no split, < 256 tiles) v4_launch's 32-channel tiles
-  const int S = v4_ksplit(d);
+  const int S = v4_ksplit(d, c);
   const int64_t items = nblk * S * (S == 1 && dtype_half(d->dtype) && nblk < 256 ? 2 : 1);
   if (items < std::min<int64_t>(384, v4_ksplit_target()) && path < 2) return false;  // too few work items even K-split: the brick kernels
   const int esz = dtype_size(d->dtype);
@@ -257,33 +257,26 @@ bool v4_eligible(const cwdm_conv3d_desc* d) {
   return sv * d->a_c0 * esz < lim && sv * d->a_c1 * esz < lim;
 }
 
-int64_t v4_workspace_bytes(const cwdm_conv3d_desc* d) {
+int64_t v4_workspace_bytes(const cwdm_conv3d_desc* d, const ConvCall& c) {
   const int esz = dtype_size(d->dtype);
   int64_t ws = 0;
   if (d->a_gn) ws += align256(d->B * src_voxels(d) * (d->a_c0 + d->a_c1) * esz);
   if (d->b_w) ws += align256(d->B * d->D * d->H * d->W * d->cout * esz);
   // K-split slices of the conv, or of its 1x1 skip pre-pass (which runs first: one region serves both)
-  int S = v4_ksplit(d);
+  int S = v4_ksplit(d, c);
   if (d->b_w) {
     cwdm_conv3d_desc e = *d;
     e.a_w = nullptr;
-    S = std::max(S, sg_skip_ksplit(&e));
+    S = std::max(S, sg_skip_ksplit(&e, c.fp32x));
   }
   // (+ the small-grid kernel's K-split arrival counters behind the slices)
-  if (S > 1) ws += align256(S * d->B * ksplit_slice_voxels(d) * d->cout * 4) + sg_sync_bytes(S);
+  if (S > 1) ws += align256(S * d->B * ksplit_slice_voxels(d, c.fp32x) * d->cout * 4) + sg_sync_bytes(S);
   // (+ a lone launch's apply-ahead sweep counters, last: conv3d_v4_forward)
   if (d->a_gn) ws += kV5AaWords * 4;
   return ws;
 }
 
-// the U-Net plan's backward: fuse the reduce pass of the SiLU(GroupNorm)
-// backward that follows this dgrad conv into its epilogue (GbwdFuse, conv3d_v4.hpp
-// V4Params::gx0); taken only by the 16-bit fast epilogue without K split
-thread_local GbwdFuse* g_gbwd = nullptr;
-thread_local GnFinFuse* g_gnfin = nullptr;
-
-int gnfin_flush(const cwdm_conv3d_desc* d, hipStream_t s) {
-  GnFinFuse* f = g_gnfin;
+int gnfin_flush(const cwdm_conv3d_desc* d, GnFinFuse* f, hipStream_t s) {
   if (!f || f->used || !d->a_gn || f->ss != d->a_gn) return CWDM_OK;
   f->used = true;
   return cwdm_gn_finalize(f->s0, f->p0, f->c0, f->s1, f->p1, f->c1, f->gamma, f->beta, f->groups, f->B, f->voxels,
@@ -329,8 +322,10 @@ int gn_fin_apply(const GnFinFuse& f, const void* x0, int c0, const void* x1, int
 }
 }  // namespace
 
-// the backward's dgrad conv whose epilogue may take the GroupNorm-backward
-// reduce (v4 only): only where the conv leaves VALU room -- at 128^3 the
+// the U-Net plan's backward: fuse the reduce pass of the SiLU(GroupNorm)
+// backward that follows this dgrad conv into its epilogue (GbwdFuse, conv3d_v4.hpp
+// V4Params::gx0); taken only by the 16-bit fast epilogue without K split (v4
+// only), and only where the conv leaves VALU room -- at 128^3 the
 // epilogue's ~13 VALU + 2 transcendentals per output element cost the
 // MFMA-bound kernel more (+30 %) than the separate reduce pass it saves; at
 // 32^3 it is a net win (same-box kernel traces).  At 64^3 it was too
@@ -338,9 +333,9 @@ int gn_fin_apply(const GnFinFuse& f, const void* x0, int c0, const void* x1, int
 // dgrads faster than the fused v4 instance runs: 12 launches 3096 us fused vs 2547 +
 // 371 us of separate reduces (r06, profiles/r06/w_gbwd_maxw_ab.txt).  Env
 // CWDM_GBWD_MAXW, default 32.  Elsewhere the dgrad is an ordinary conv (v5 may take it).
-bool gbwd_grid_ok(const cwdm_conv3d_desc* d) {
+bool gbwd_grid_ok(const cwdm_conv3d_desc* d, const GbwdFuse* g) {
   static const int gb_maxw = env_int("CWDM_GBWD_MAXW", 32);
-  return g_gbwd && !g_gbwd->used && dtype_half(d->dtype) && d->W <= gb_maxw && d->a_mode == 0 && d->res_mode < 0 &&
+  return g && !g->used && dtype_half(d->dtype) && d->W <= gb_maxw && d->a_mode == 0 && d->res_mode < 0 &&
          !d->stats;
 }
 
@@ -365,9 +360,9 @@ int gn_apply(const void* x0, int c0, const void* x1, int c1, const float* gn, in
 
 // launch of the DMA-staged kernel on prepared sources: a0 (c0 channels,
 // chunk-major if a0_cm) and a1 (c1 channels, channels-last), residual res/rmode;
-// partial: fp32 scratch of v4_ksplit(d) output slices (unused without a K split)
+// partial: fp32 scratch of v4_ksplit(d, c) output slices (unused without a K split)
 int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
-              const void* res, int rmode, void* partial, hipStream_t s) {
+              const void* res, int rmode, void* partial, ConvCall& c, hipStream_t s) {
   const int esz = dtype_size(d->dtype);
   const int ck = 32 / esz;
   const int64_t SV = src_voxels(d);
@@ -391,14 +386,14 @@ int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
   p.out1 = d->out1; p.out_c0 = d->out_c0;
   p.accumulate = d->accumulate;
   p.stamps = g_stamps.load(std::memory_order_relaxed);
-  if (sg_eligible(d)) return sg_launch(p, d, partial, s);
+  if (sg_eligible(d, c.fp32x)) return sg_launch(p, d, partial, c, s);
   // the warp-specialised kernel (conv3d_v5.hip) where it applies (not the
   // backward's fused GroupNorm-reduce dgrad, not the stamps diagnostics build)
   // an upsampling conv as eight phase convs on the source grid, where its phase weights came along
-  if (v5_phase_ok(d, rmode)) return v5_launch(d, a0, c0, a1, c1, a0_cm, nullptr, nullptr, -1, s, nullptr, true);
-  if (v5_eligible(d, false))   // (refuses the dgrad that takes the fused GroupNorm-backward reduce)
-    return v5_launch(d, a0, c0, a1, c1, a0_cm, nullptr, res, rmode, s);
-  const int S = v4_ksplit(d);
+  if (v5_phase_ok(d, rmode, c)) return v5_launch(d, a0, c0, a1, c1, a0_cm, nullptr, nullptr, -1, c, s, nullptr, true);
+  if (v5_eligible(d, false, c))   // (refuses the dgrad that takes the fused GroupNorm-backward reduce)
+    return v5_launch(d, a0, c0, a1, c1, a0_cm, nullptr, res, rmode, c, s);
+  const int S = v4_ksplit(d, c);
   p.ksplit = S;
   p.kper = (p.nch + S - 1) / S;
   if (S > 1) {
@@ -434,7 +429,7 @@ int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
   // the fast epilogue addresses output / residual through 32-bit buffer offsets per batch
   const bool fast = !p.out_f32 && !p.accumulate && !p.out1 &&
                     (long long)p.D * p.H * p.W * p.cout * 2 < 0xFFFFE000LL;
-  prof_begin(s);
+  prof_begin(c.prof, s);
   auto launch16 = [&](auto tag) {
     using T = decltype(tag);
     if (p.gx0) {   // fused GroupNorm-backward reduce (dgrad, same-grid source: amode 0)
@@ -452,8 +447,8 @@ int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
     }
   };
   // (gbwd_grid_ok: where the fused reduce pays)
-  if (gbwd_grid_ok(d) && (ct32 || fast) && S == 1 && rmode < 0 && !p.stats && p.amode == 0) {
-    GbwdFuse& g = *g_gbwd;
+  if (gbwd_grid_ok(d, c.gbwd) && (ct32 || fast) && S == 1 && rmode < 0 && !p.stats && p.amode == 0) {
+    GbwdFuse& g = *c.gbwd;
     const int nc = ct32 ? 32 : 64;
     const int C = d->cout;
     const long long need = (long long)p.B * p.tx * p.ty * p.tz * C * 8;
@@ -475,7 +470,7 @@ int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
     if (p.amode == 1) hipLaunchKernelGGL((conv3d_v4_kernel<float, 1, false>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((conv3d_v4_kernel<float, 0, false>), grid, dim3(256), 0, s, p);
   }
-  prof_end(s, 2.0 * p.B * p.D * p.H * p.W * (double)p.cout * 27.0 * (c0 + c1));
+  prof_end(c.prof, s, 2.0 * p.B * p.D * p.H * p.W * (double)p.cout * 27.0 * (c0 + c1));
   CWDM_LAUNCHED();
   if (S > 1) {
     // finish: slice sum over the whole chip, then the per-tile epilogue
@@ -506,10 +501,7 @@ int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
   return CWDM_OK;
 }
 
-thread_local void* g_act_keep = nullptr;  // set by the U-Net plan's training forward (ActKeepScope)
-thread_local int g_act_kept = 0;
-
-int conv3d_v4_forward(const cwdm_conv3d_desc* d, hipStream_t s) {
+int conv3d_v4_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s) {
   const int esz = dtype_size(d->dtype);
   unsigned char* ws = reinterpret_cast<unsigned char*>(d->workspace);
   const int64_t SV = src_voxels(d);
@@ -521,33 +513,33 @@ int conv3d_v4_forward(const cwdm_conv3d_desc* d, hipStream_t s) {
   // GroupNorm + SiLU inside the warp-specialised conv (no activated copy):
   // inference only -- the training forward keeps the activated input for wgrad
   const float* agn = nullptr;
-  if (d->a_gn && !g_act_keep && v5_eligible(d, true)) agn = d->a_gn;
+  if (d->a_gn && !c.act_keep && v5_eligible(d, true, c)) agn = d->a_gn;
   // or the warp-specialised conv writes the activated copy itself, ahead of its sweep (apply-ahead:
   // no pre-pass over HBM; the training forward keeps the copy it writes)
   V5Aa aa{};
-  aa.units = (d->a_gn && !agn) ? v5_aa_units(d, &aa.lead) : 0;
+  aa.units = (d->a_gn && !agn) ? v5_aa_units(d, c, &aa.lead) : 0;
   // an offered GroupNorm finalize (GnFinFuse): fused into the pre-pass below where it fits, else run now
-  GnFinFuse* fin = (g_gnfin && !g_gnfin->used && d->a_gn && g_gnfin->ss == d->a_gn) ? g_gnfin : nullptr;
+  GnFinFuse* fin = (c.gnfin && !c.gnfin->used && d->a_gn && c.gnfin->ss == d->a_gn) ? c.gnfin : nullptr;
   if (fin && (agn || aa.units || !gn_fin_fusable(*fin, d->dtype, c0, c1))) {
-    if ((rc = gnfin_flush(d, s))) return rc;
+    if ((rc = gnfin_flush(d, fin, s))) return rc;
     fin = nullptr;
   }
   if (d->a_gn && !agn) {
     // the activated input: in the workspace, or (training) where the plan keeps
     // it for the backward's DMA-staged wgrad
     void* act = ws;
-    if (g_act_keep) {
-      act = g_act_keep;
-      g_act_kept = 1;
+    if (c.act_keep) {
+      act = c.act_keep;
+      c.act_kept = true;
     } else {
       ws += align256(d->B * SV * (c0 + c1) * esz);
     }
     if (aa.units) {
       aa.x0 = a0; aa.c0 = c0; aa.x1 = a1; aa.c1 = c1; aa.gn = d->a_gn;
       // the sweep counters: the plan's zeroed sync block, else this launch's workspace tail (zeroed here)
-      aa.cnt = plan_aa_counters();
+      aa.cnt = plan_aa_counters(c.sync);
       if (!aa.cnt) {
-        const int64_t need = v4_workspace_bytes(d);
+        const int64_t need = v4_workspace_bytes(d, c);
         CWDM_REQUIRE(d->workspace && d->ws_bytes >= need, CWDM_E_WORKSPACE, "conv3d (apply-ahead): workspace too small");
         aa.cnt = reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(d->workspace) + need - kV5AaWords * 4);
         CWDM_HIP(hipMemsetAsync(aa.cnt, 0, kV5AaWords * 4, s));
@@ -571,20 +563,20 @@ int conv3d_v4_forward(const cwdm_conv3d_desc* d, hipStream_t s) {
     e.bias = nullptr; e.bias_bstride = 0; e.stats = nullptr;
     e.out = skip; e.out_dtype = d->dtype; e.out1 = nullptr; e.out_c0 = 0; e.accumulate = 0;
     e.workspace = nullptr; e.ws_bytes = 0;
-    if (sg_skip_eligible(&e)) {
-      if ((rc = sg_skip_launch(&e, skip, ws, s))) return rc;   // ws: the K-split region, free until the conv
+    if (sg_skip_eligible(&e, c.fp32x)) {
+      if ((rc = sg_skip_launch(&e, skip, ws, c, s))) return rc;   // ws: the K-split region, free until the conv
     } else if (pw_eligible(&e)) {
-      if ((rc = pw_forward(&e, s))) return rc;
+      if ((rc = pw_forward(&e, c, s))) return rc;
     } else if (pw_split_eligible(&e)) {
-      if ((rc = pw_split_forward(&e, s))) return rc;
-    } else if ((rc = legacy_conv3d_forward(&e, (cwdm_stream_t)s))) {
+      if ((rc = pw_split_forward(&e, c.prof, s))) return rc;
+    } else if ((rc = legacy_conv3d_forward(&e, c.prof, s))) {
       return rc;
     }
     res = skip; rmode = 0;
   }
-  if (agn) return v5_launch(d, a0, c0, a1, c1, 0, agn, res, rmode, s);
-  if (aa.units) return v5_launch(d, a0, c0, nullptr, 0, 1, nullptr, res, rmode, s, &aa);
-  return v4_launch(d, a0, c0, a1, c1, a0_cm, res, rmode, v4_ksplit(d) > 1 ? ws : nullptr, s);
+  if (agn) return v5_launch(d, a0, c0, a1, c1, 0, agn, res, rmode, c, s);
+  if (aa.units) return v5_launch(d, a0, c0, nullptr, 0, 1, nullptr, res, rmode, c, s, &aa);
+  return v4_launch(d, a0, c0, a1, c1, a0_cm, res, rmode, v4_ksplit(d, c) > 1 ? ws : nullptr, c, s);
 }
 
 // ---------------------------------------------------------------------------

@@ -108,9 +108,10 @@ constexpr int kV5AaWords = 4096;   // apply-ahead sweep counters of one launch (
 struct V5Aa { const void* x0; int c0; const void* x1; int c1; const float* gn; int lead, units; unsigned* cnt; };
 
 // the launchers that take these (the rest of the cross-unit interface: internal.hpp)
-int sg_launch(const V4Params& v, const cwdm_conv3d_desc* d, void* partial, hipStream_t s);   // conv3d_sg.hip
+int sg_launch(const V4Params& v, const cwdm_conv3d_desc* d, void* partial, const ConvCall& c,
+              hipStream_t s);   // conv3d_sg.hip
 int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
-              const float* agn, const void* res, int rmode, hipStream_t s, const V5Aa* aa = nullptr,
+              const float* agn, const void* res, int rmode, ConvCall& c, hipStream_t s, const V5Aa* aa = nullptr,
               bool phase = false);  // conv3d_v5.hip
 
 struct V4Cfg {

@@ -1290,10 +1290,6 @@ std::atomic<int> g_up_phase{env_not0("CWDM_UP_PHASE") ? 1 : 0};
 std::atomic<int> g_up_phase_launches{0};
 std::atomic<int> g_v5_aa_extra{0};
 std::atomic<int> g_v5_aa_spin{0};
-// the U-Net plan asks for per-workgroup GroupNorm partials (V4Params::stats_wg) around its convs and
-// reads back how many rows a launch wrote (0: the per-tile layout of cwdm_conv3d_parts)
-thread_local int g_stats_wg = 0;
-thread_local int64_t g_stats_rows = 0;
 
 namespace {
 int v5_ncu() {
@@ -1326,7 +1322,7 @@ int v5_aa_grid(int64_t nblk) {
 // every eligible conv with the GroupNorm applied by the cwdm_gn_apply pre-pass: the
 // in-LDS transform costs the helper waves more issue cycles than the MFMA waves
 // leave them -- measured 611 vs 588 us on the 64->64 128^3-subband conv)
-bool v5_eligible(const cwdm_conv3d_desc* d, bool gn) {
+bool v5_eligible(const cwdm_conv3d_desc* d, bool gn, const ConvCall& c) {
   const int mode = v5_mode();
   const int path = g_conv_path.load(std::memory_order_relaxed);
   if (d->dtype == CWDM_F32) {
@@ -1354,15 +1350,15 @@ bool v5_eligible(const cwdm_conv3d_desc* d, bool gn) {
   // source voxel 8x: the pre-pass at the half resolution is 8x cheaper), and
   // not in mode 3 (pre-pass + this kernel on the activated copy)
   if (gn && (d->a_mode == 1 || mode == 3)) return false;
-  if (!dtype_half(d->dtype) || sg_eligible(d)) return false;
-  if (path != 2 && v4_ksplit(d) != 1) return false;   // (path 2: forced, no K split of its own)
+  if (!dtype_half(d->dtype) || sg_eligible(d, c.fp32x)) return false;
+  if (path != 2 && v4_ksplit(d, c) != 1) return false;   // (path 2: forced, no K split of its own)
   if (d->out_dtype != d->dtype || d->accumulate || d->out1) return false;
   if (d->a_mode != 0 && d->a_mode != 1) return false;
   if (d->res_mode < -1 || d->res_mode > 1) return false;
   if (d->W < kWideMinW || d->H % 4 || d->D % 4 || d->cout % 64) return false;
   if (d->D * d->H * d->W * d->cout * 2 >= 0xFFFFE000LL) return false;
   if (d->a_c0 + d->a_c1 < 32) return false;   // >= 2 chunks per tile: a tile's drain spans two chunks
-  if (gbwd_grid_ok(d)) return false;   // the backward's fused dgrad instance is v4's
+  if (gbwd_grid_ok(d, c.gbwd)) return false;   // the backward's fused dgrad instance is v4's
   const int ncu = v5_ncu();
   // tiles per CU below which v4 (two workgroups per CU) keeps the conv (env
   // CWDM_V5_MIN_TPC, A/B knob; 1 since r04: config 5's 56^3 64-channel convs,
@@ -1382,19 +1378,19 @@ unsigned v5_grid(long long nblk) {
 // The phase instance (conv3d_v5_kernel<T, 2, false>) takes an upsampling conv the gather instance
 // (MODE 1) would run -- 16-bit, no residual, no 1x1 skip product -- when its phase weights came along
 // and the SOURCE grid tiles (W / 2 >= kWideMinW, H / 2 and D / 2 multiples of 4).  Statistics: per
-// workgroup wherever the plan asks for them and the rows fit; per tile one row per (source tile,
+// workgroup wherever the caller asks for them (ConvCall::stats_wg) and the rows fit; per tile one row per (source tile,
 // phase), laid out as the 2 tx x 2 ty x 2 tz output bricks -- only where those are the rows the caller
 // holds (cwdm_conv3d_parts of the output grid: ceil(W / 32) == 2 ceil(W / 64)), else the gather path.
-bool v5_phase_ok(const cwdm_conv3d_desc* d, int rmode) {
+bool v5_phase_ok(const cwdm_conv3d_desc* d, int rmode, const ConvCall& c) {
   if (!d->a_w_phase || !g_up_phase.load(std::memory_order_relaxed)) return false;
   if (!dtype_half(d->dtype) || d->a_mode != 1 || d->b_w || rmode != -1 || d->res_mode != -1) return false;
-  if (!v5_eligible(d, false)) return false;
+  if (!v5_eligible(d, false, c)) return false;
   const int64_t SD = d->D / 2, SH = d->H / 2, SW = d->W / 2;
   if (SW < kWideMinW || SH % 4 || SD % 4) return false;
   if (d->stats) {
     const int64_t stx = (SW + 31) / 32, otx = (d->W + 31) / 32, otiles = otx * (d->H / 4) * (d->D / 4);
     const long long nblk = (long long)d->B * stx * (SH / 4) * (SD / 4) * (d->cout / 64) * 8;
-    const bool wg = g_stats_wg && d->B == 1 && d->cout / 64 <= 2 && (long long)v5_grid(nblk) <= otiles;
+    const bool wg = c.stats_wg && d->B == 1 && d->cout / 64 <= 2 && (long long)v5_grid(nblk) <= otiles;
     if (!wg && otx != 2 * stx) return false;
   }
   return true;
@@ -1404,12 +1400,12 @@ bool v5_phase_ok(const cwdm_conv3d_desc* d, int rmode) {
 // agn: [B][c0 + c1][2] GroupNorm scale / shift applied in LDS (null: none)
 // apply-ahead (conv3d_v5_kernel<.., AA>) for a GroupNorm'd conv input: the per-chunk share AA (1, 2, 4,
 // 8 steps of 256 lanes) its sweep needs, or 0 where it does not apply (env CWDM_V5_AA=0: never)
-int v5_aa_units(const cwdm_conv3d_desc* d, int* lead) {
+int v5_aa_units(const cwdm_conv3d_desc* d, const ConvCall& c, int* lead) {
   const int mode = g_v5_aa.load(std::memory_order_relaxed);
   if (!mode || !d->a_gn || d->B != 1 || d->a_mode != 0 || !dtype_half(d->dtype)) return 0;
   const int C = d->a_c0 + d->a_c1;
   if (d->a_c0 % 8 || d->a_c1 % 8 || C % 16 || C > 2048) return 0;
-  if (!v5_eligible(d, false)) return 0;
+  if (!v5_eligible(d, false, c)) return 0;
   // the helpers' share per chunk fits beside the drain from 8 input chunks (r05 stamps: the
   // 4-chunk 64-channel convs left them ~4k cycles behind the MFMA waves per chunk); env
   // CWDM_V5_AA_MINCH (A/B knob)
@@ -1444,7 +1440,7 @@ int v5_aa_units(const cwdm_conv3d_desc* d, int* lead) {
 }
 
 int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
-              const float* agn, const void* res, int rmode, hipStream_t s, const V5Aa* aa, bool phase) {
+              const float* agn, const void* res, int rmode, ConvCall& c, hipStream_t s, const V5Aa* aa, bool phase) {
   const int esz = dtype_size(d->dtype);
   const int ck = 32 / esz;
   const int64_t SV = d->a_mode == 1 ? d->D * d->H * d->W / 8 : d->D * d->H * d->W;
@@ -1498,14 +1494,14 @@ int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
   // per-tile layout has -- the tiles of the OUTPUT grid, which the caller sized its rows by): the
   // finalize then reduces gridDim.x rows instead of one per tile
   const long long otiles = phase ? ((d->W + 31) / 32) * (d->H / 4) * (d->D / 4) : (long long)p.tx * p.ty * p.tz;
-  if (g_stats_wg && d->stats && p.B == 1 && p.nct <= 2 && (long long)grid.x <= otiles) {
+  if (c.stats_wg && d->stats && p.B == 1 && p.nct <= 2 && (long long)grid.x <= otiles) {
     p.stats_wg = 1;
-    g_stats_rows = grid.x;
+    c.stats_rows = grid.x;
   }
   // (v5_eligible never grants the in-LDS GroupNorm to an upsampling conv: its halo repeats every source voxel 8x)
   CWDM_REQUIRE(!(agn && p.amode == 1 && dtype_half(d->dtype)), CWDM_E_UNSUPPORTED,
                "conv3d_v5: GroupNorm in LDS on an upsampling conv");
-  prof_begin(s);
+  prof_begin(c.prof, s);
   auto go = [&](auto tag) {
     using T = decltype(tag);
     if (agn) {   // (never an upsampling conv: v5_eligible, checked above)
@@ -1544,7 +1540,7 @@ int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
     go(f16_t{});
   }
   // (the flops executed: the phase instance runs 8 folded taps per output voxel, not 27)
-  prof_end(s, phase ? 2.0 * d->B * d->D * d->H * d->W * (double)p.cout * 8.0 * (c0 + c1)
+  prof_end(c.prof, s, phase ? 2.0 * d->B * d->D * d->H * d->W * (double)p.cout * 8.0 * (c0 + c1)
                     : 2.0 * p.B * p.D * p.H * p.W * (double)p.cout * 27.0 * (c0 + c1));
   CWDM_LAUNCHED();
   return CWDM_OK;
@@ -1577,14 +1573,6 @@ extern "C" int cwdm_debug_v5_aa(int on) {
 extern "C" int cwdm_debug_up_phase(int on) {
   if (on < 0) return cwdm::g_up_phase_launches.load(std::memory_order_relaxed);
   return cwdm::g_up_phase.exchange(on ? 1 : 0);
-}
-
-extern "C" int64_t cwdm_debug_stats_wg(int on) {
-  if (on < 0) return cwdm::g_stats_rows;
-  const int prev = cwdm::g_stats_wg;
-  cwdm::g_stats_wg = on ? 1 : 0;
-  cwdm::g_stats_rows = 0;
-  return prev;
 }
 
 extern "C" int cwdm_debug_v5_aa_timeout(int extra, int spin) {

@@ -1,7 +1,9 @@
-// libcwdm's cross-unit interface: every function and global that one
-// translation unit defines and another uses is declared here, once (those whose
-// signature needs V4Params / V5Aa: conv3d_v4.hpp).  The defining unit includes
-// this header too, so a signature or type that drifts fails to compile.
+// libcwdm's cross-unit interface: every function that one translation unit
+// defines and another uses is declared here, once (those whose signature needs
+// V4Params / V5Aa: conv3d_v4.hpp), with the two process-wide atomics they share.
+// No per-thread state crosses units: what a conv call takes and reports beyond
+// its desc travels in a ConvCall.  The defining unit includes this header too,
+// so a signature or type that drifts fails to compile.
 #pragma once
 #include <atomic>
 #include <vector>
@@ -16,16 +18,42 @@ namespace cwdm {
 extern std::atomic<int> g_conv_path;
 extern std::atomic<unsigned long long*> g_stamps;
 
-// conv3d.hip: the brick / split-K kernels, and the batched weight packs
-int legacy_conv3d_forward(const cwdm_conv3d_desc* d, cwdm_stream_t stream);
-extern thread_local std::vector<PackJob>* g_pack_batch;
+// What one conv call takes beyond its desc, and what it reports back.  The
+// eligibility predicates below are functions of (desc, context): a question
+// asked at layout time gets the run-time answer when it passes the same fields.
+struct ConvCall {
+  // offered by the caller (the defaults: nothing)
+  GnFinFuse* gnfin = nullptr;    // a pending GroupNorm finalize of d->a_gn (taken: gnfin->used)
+  GbwdFuse* gbwd = nullptr;      // the GroupNorm-backward reduce for a dgrad's epilogue (gbwd->used / nblk)
+  GapplyFuse* gapply = nullptr;  // the GroupNorm-backward apply for a 1x1 skip dgrad (gapply->used)
+  void* act_keep = nullptr;      // where the GroupNorm pre-pass writes the activated input (null: the workspace)
+  // the caller's zeroed sync block (plan_sync_bytes): the small-grid K-split arrival counters -- each
+  // K-split launch leaves them zero again -- then the apply-ahead sweep counters; null: from the workspace
+  unsigned* sync = nullptr;
+  bool fp32x = false;            // a 16-bit small-grid conv may write fp32 (the K-expanded split convs only)
+  bool stats_wg = false;         // per-workgroup GroupNorm partials wanted
+  ProfHook* prof = nullptr;
+  // reported by the call
+  bool act_kept = false;         // the pre-pass wrote to act_keep
+  int64_t stats_rows = 0;        // rows of per-workgroup partials written (0: the per-tile layout)
+};
+// cwdm_conv3d_forward with its context
+int conv3d_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s);
+
+// conv3d.hip: the brick / split-K kernels, and the weight packs as jobs (the public packs'
+// checks and error codes; a caller batches its jobs through pack_batch_run)
+int legacy_conv3d_forward(const cwdm_conv3d_desc* d, ProfHook* prof, hipStream_t s);
+int pack_job(const float* w, int cout, int cin, int ksize, int dtype, void* packed, PackJob& j);
+int pack_s2_job(const float* w, int cout, int cin, int dtype, void* packed, int transpose, PackJob& j);
+int pack_dgrad_job(const float* w, int cout, int cin, int ksize, int dtype, void* packed, PackJob& j);
+int pack_phase_job(const float* w, int cout, int cin, int dtype, void* packed, PackJob& j);
 int pack_batch_run(std::vector<PackJob>& jobs, int dtype, PackJob* table, std::vector<PackJob>& cache, hipStream_t s);
 
 // conv3d_head.hip: the output head, its fused sampler step, the split-bf16 preparations
 bool head_eligible(const cwdm_conv3d_desc* d);
-int head_conv_forward(const cwdm_conv3d_desc* d, hipStream_t s);
+int head_conv_forward(const cwdm_conv3d_desc* d, ProfHook* prof, hipStream_t s);
 bool head_sampler_eligible(const cwdm_conv3d_desc* d, const cwdm_sampler_args* a);
-int head_sampler_forward(const cwdm_conv3d_desc* d, const cwdm_sampler_args* a, hipStream_t s);
+int head_sampler_forward(const cwdm_conv3d_desc* d, const cwdm_sampler_args* a, ProfHook* prof, hipStream_t s);
 int head_split3_prep(const float* x, const float* gn, int64_t B, int64_t V, int C, void* x3, hipStream_t s);
 int head_split3_pack(const float* w, int cout, int cin, float* tmp, void* out, hipStream_t s, int k);
 int split3_prep(const float* x0, int c0, const float* x1, int c1, const float* gn, int64_t B, int64_t V, int cm,
@@ -33,70 +61,44 @@ int split3_prep(const float* x0, int c0, const float* x1, int c1, const float* g
 
 // pointwise.hip: 1x1 convs (pw_gapply_ok: the skip dgrad can take a GapplyFuse)
 bool pw_eligible(const cwdm_conv3d_desc* d);
-int pw_forward(const cwdm_conv3d_desc* d, hipStream_t s);
+int pw_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s);
 bool pw_gapply_ok(const cwdm_conv3d_desc* d);
 bool pw_split_eligible(const cwdm_conv3d_desc* d);
-int pw_split_forward(const cwdm_conv3d_desc* d, hipStream_t s);
+int pw_split_forward(const cwdm_conv3d_desc* d, ProfHook* prof, hipStream_t s);
 
 // conv3d_v4.hip: the DMA-staged conv and its pre-passes
-bool v4_eligible(const cwdm_conv3d_desc* d);
+bool v4_eligible(const cwdm_conv3d_desc* d, const ConvCall& c);
 int64_t v4_items(const cwdm_conv3d_desc* d);
-int v4_ksplit(const cwdm_conv3d_desc* d);
-int64_t v4_workspace_bytes(const cwdm_conv3d_desc* d);
-int conv3d_v4_forward(const cwdm_conv3d_desc* d, hipStream_t s);
+int v4_ksplit(const cwdm_conv3d_desc* d, const ConvCall& c);
+int64_t v4_workspace_bytes(const cwdm_conv3d_desc* d, const ConvCall& c);
+int conv3d_v4_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s);
 int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
-              const void* res, int rmode, void* partial, hipStream_t s);
-bool gbwd_grid_ok(const cwdm_conv3d_desc* d);
+              const void* res, int rmode, void* partial, ConvCall& c, hipStream_t s);
+bool gbwd_grid_ok(const cwdm_conv3d_desc* d, const GbwdFuse* g);
 bool apply_skip_ok(int dtype, int C, int cout, int64_t B, int64_t vpb);
 int gn_apply_skip(const void* x0, int c0, const void* x1, int c1, const float* gn, int64_t B, int64_t vpb, int dtype,
                   const void* wskip, int cout, void* act, void* skip, hipStream_t s);
-// run the offered GroupNorm finalize now if it is pending for d (d->a_gn == its ss)
-int gnfin_flush(const cwdm_conv3d_desc* d, hipStream_t s);
-// where conv3d_v4_forward's GroupNorm pre-pass writes the activated input
-// (null: its own workspace), and whether it did
-extern thread_local void* g_act_keep;
-extern thread_local int g_act_kept;
-struct ActKeepScope {
-  void* ptr;
-  explicit ActKeepScope(void* p) : ptr(p) { g_act_keep = p; g_act_kept = 0; }
-  ~ActKeepScope() { g_act_keep = nullptr; }
-  bool used() const { return g_act_kept != 0; }
-};
+// run the offered GroupNorm finalize f now if it is pending for d (d->a_gn == its ss)
+int gnfin_flush(const cwdm_conv3d_desc* d, GnFinFuse* f, hipStream_t s);
 
 // conv3d_v5.hip: the warp-specialised conv
-bool v5_eligible(const cwdm_conv3d_desc* d, bool gn);
-int v5_aa_units(const cwdm_conv3d_desc* d, int* lead);
+bool v5_eligible(const cwdm_conv3d_desc* d, bool gn, const ConvCall& c);
+int v5_aa_units(const cwdm_conv3d_desc* d, const ConvCall& c, int* lead);
 // the phase instance takes this upsampling conv (cwdm_conv3d_desc.a_w_phase; rmode: the residual
 // mode after the 1x1 skip pre-pass)
-bool v5_phase_ok(const cwdm_conv3d_desc* d, int rmode);
-extern thread_local int g_stats_wg;         // per-workgroup GroupNorm partials wanted
-extern thread_local int64_t g_stats_rows;   // ... and the rows the last launch wrote (0: per tile)
+bool v5_phase_ok(const cwdm_conv3d_desc* d, int rmode, const ConvCall& c);
 
-// conv3d_sg.hip: the small-grid conv
-bool sg_eligible(const cwdm_conv3d_desc* d);
-int sg_ksplit(const cwdm_conv3d_desc* d);
-bool sg_skip_eligible(const cwdm_conv3d_desc* d);
-int sg_skip_ksplit(const cwdm_conv3d_desc* d);
-int sg_skip_launch(const cwdm_conv3d_desc* d, void* out, void* partial, hipStream_t s);
-int64_t ksplit_slice_voxels(const cwdm_conv3d_desc* d);
+// conv3d_sg.hip: the small-grid conv (fp32x: ConvCall::fp32x)
+bool sg_eligible(const cwdm_conv3d_desc* d, bool fp32x);
+int sg_ksplit(const cwdm_conv3d_desc* d, bool fp32x);
+bool sg_skip_eligible(const cwdm_conv3d_desc* d, bool fp32x);
+int sg_skip_ksplit(const cwdm_conv3d_desc* d, bool fp32x);
+int sg_skip_launch(const cwdm_conv3d_desc* d, void* out, void* partial, const ConvCall& c, hipStream_t s);
+int64_t ksplit_slice_voxels(const cwdm_conv3d_desc* d, bool fp32x);
 int64_t sg_sync_bytes(int ksplit);
 int64_t plan_sync_bytes();
-unsigned* plan_aa_counters();
-// the K-split arrival counters for one launch list: one block in the plan's
-// workspace, zeroed once (a memset node) before the list -- each K-split launch
-// leaves its counters zero again -- and handed to the launches for the duration
-// of the call
-extern thread_local unsigned* g_sg_sync;
-struct SgSyncScope {
-  SgSyncScope(void* block) { g_sg_sync = reinterpret_cast<unsigned*>(block); }
-  ~SgSyncScope() { g_sg_sync = nullptr; }
-};
-// the kernel's fp32 output / residual, for the K-expanded split convs only
-extern thread_local bool g_sg_fp32x;
-struct SgFp32xScope {
-  SgFp32xScope() { g_sg_fp32x = true; }
-  ~SgFp32xScope() { g_sg_fp32x = false; }
-};
+// the apply-ahead sweep counters of a sync block (ConvCall::sync)
+unsigned* plan_aa_counters(unsigned* sync);
 
 // ---- what else the U-Net plan drives --------------------------------------
 // embed.hip

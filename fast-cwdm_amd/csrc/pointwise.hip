@@ -36,7 +36,6 @@ struct PwParams {
   const void* gx0; const void* gx1; const void* gdu; const float* gss; const float* gcoef;
 };
 
-thread_local GapplyFuse* g_gapply = nullptr;
 // the fused-apply skip dgrad's row-major epilogue on / off (cwdm_debug_pw_lt), and its launches
 std::atomic<int> g_pw_lt{env_not0("CWDM_PW_LT") ? 1 : 0};
 std::atomic<int> g_pw_lt_launches{0};
@@ -509,7 +508,7 @@ bool pw_gapply_ok(const cwdm_conv3d_desc* d) {
          d->D * d->H * d->W >= 256 && !d->bias;
 }
 
-int pw_forward(const cwdm_conv3d_desc* d, hipStream_t s) {
+int pw_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s) {
   PwParams p{};
   p.V = d->D * d->H * d->W;
   p.rows = d->B * p.V;
@@ -520,11 +519,11 @@ int pw_forward(const cwdm_conv3d_desc* d, hipStream_t s) {
   p.NT = 32 * pick_nf(d->cout);   // the packed layout's rows per channel tile (cwdm_conv3d_pack)
   p.bias = d->bias; p.bias_bs = d->bias_bstride;
   p.out = d->out; p.out1 = d->out1; p.out_c0 = d->out_c0; p.accumulate = d->accumulate;
-  if (g_gapply && !g_gapply->used && p.N % 8 == 0 && (!d->out1 || d->out_c0 % 8 == 0) && p.V >= 256 &&
-      !d->bias) {
-    p.gx0 = g_gapply->x0; p.gx1 = g_gapply->x1; p.gdu = g_gapply->du;
-    p.gss = g_gapply->ss; p.gcoef = g_gapply->coef;
-    g_gapply->used = true;
+  GapplyFuse* g = c.gapply;
+  if (g && !g->used && p.N % 8 == 0 && (!d->out1 || d->out_c0 % 8 == 0) && p.V >= 256 && !d->bias) {
+    p.gx0 = g->x0; p.gx1 = g->x1; p.gdu = g->du;
+    p.gss = g->ss; p.gcoef = g->coef;
+    g->used = true;
   }
   const bool ga = p.gdu != nullptr;
   // row-major LDS epilogue (pw_kernel LT): cwdm_debug_pw_lt / env CWDM_PW_LT = 0 restores the swapped-lane one
@@ -538,7 +537,7 @@ int pw_forward(const cwdm_conv3d_desc* d, hipStream_t s) {
   p.nnb = (int)ceil_div(d->cout, 32 * nm);
   const long long nblk = ceil_div(p.rows, 256) * p.nnb;
   CWDM_REQUIRE(nblk < (1LL << 31), CWDM_E_UNSUPPORTED, "conv3d (pointwise): grid too large");
-  prof_begin(s);
+  prof_begin(c.prof, s);
   if (d->dtype == CWDM_F16) {
     if (lt && nm == 2) hipLaunchKernelGGL((pw_kernel<f16_t, true, 2, true>), dim3((unsigned)nblk), dim3(256), 0, s, p);
     else if (lt) hipLaunchKernelGGL((pw_kernel<f16_t, true, 4, true>), dim3((unsigned)nblk), dim3(256), 0, s, p);
@@ -552,7 +551,7 @@ int pw_forward(const cwdm_conv3d_desc* d, hipStream_t s) {
     else if (ga) hipLaunchKernelGGL((pw_kernel<bf16_t, true, 4>), dim3((unsigned)nblk), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((pw_kernel<bf16_t, false, 4>), dim3((unsigned)nblk), dim3(256), 0, s, p);
   }
-  prof_end(s, 2.0 * p.rows * (double)p.N * p.K);
+  prof_end(c.prof, s, 2.0 * p.rows * (double)p.N * p.K);
   CWDM_LAUNCHED();
   return CWDM_OK;
 }
@@ -567,7 +566,7 @@ bool pw_split_eligible(const cwdm_conv3d_desc* d) {
   return K % 16 == 0 && d->b_c0 % 16 == 0 && d->cout % 32 == 0 && d->B * d->D * d->H * d->W < (1LL << 40);
 }
 
-int pw_split_forward(const cwdm_conv3d_desc* d, hipStream_t s) {
+int pw_split_forward(const cwdm_conv3d_desc* d, ProfHook* prof, hipStream_t s) {
   PwParams p{};
   p.V = d->D * d->H * d->W;
   p.rows = d->B * p.V;
@@ -582,10 +581,10 @@ int pw_split_forward(const cwdm_conv3d_desc* d, hipStream_t s) {
   p.nnb = (int)ceil_div(d->cout, 32 * nm);
   const long long nblk = ceil_div(p.rows, 256) * p.nnb;
   CWDM_REQUIRE(nblk < (1LL << 31), CWDM_E_UNSUPPORTED, "conv3d (pointwise split): grid too large");
-  prof_begin(s);
+  prof_begin(prof, s);
   if (nm == 2) hipLaunchKernelGGL((pw_split_kernel<2>), dim3((unsigned)nblk), dim3(256), 0, s, p);
   else hipLaunchKernelGGL((pw_split_kernel<4>), dim3((unsigned)nblk), dim3(256), 0, s, p);
-  prof_end(s, 2.0 * p.rows * (double)p.N * p.K);
+  prof_end(prof, s, 2.0 * p.rows * (double)p.N * p.K);
   CWDM_LAUNCHED();
   return CWDM_OK;
 }

@@ -85,8 +85,8 @@ struct AvgStep {  // additive skip (cwdm_skip_avg, skip_avg.hip): out = (a + b) 
   int a, b, out, level, channels;
 };
 
-struct Step { int kind; int idx; };  // kind 0 = gn, 1 = conv, 2 = pool pre-pass, 3 = space-to-depth, 4 = haar,
-                                     // 5 = additive skip
+enum StepKind { kGn, kConv, kPool /* pre-pass */, kS2d /* space-to-depth */, kHaar, kAvg /* additive skip */ };
+struct Step { StepKind kind; int idx; };
 
 // one ResBlock, for the backward (reverse order) and the gradient segments
 struct Block {
@@ -213,7 +213,7 @@ void build(cwdm_unet* u) {
     cs.cout = mc; cs.level = 0; cs.stats = true;
     h = cs.out = new_tensor(0, mc);
     u->convs.push_back(cs);
-    u->steps.push_back({1, (int)u->convs.size() - 1});
+    u->steps.push_back({kConv, (int)u->convs.size() - 1});
     u->trace.push_back(h);
     u->trace_level.push_back(0);
   }
@@ -229,13 +229,13 @@ void build(cwdm_unet* u) {
     g.level = lvl;
     g.ss_id = (int)u->gns.size();
     u->gns.push_back(g);
-    u->steps.push_back({0, g.ss_id});
+    u->steps.push_back({kGn, g.ss_id});
     return g.ss_id;
   };
 
   auto haar_step = [&](const HaarStep& hs) {
     u->haars.push_back(hs);
-    u->steps.push_back({4, (int)u->haars.size() - 1});
+    u->steps.push_back({kHaar, (int)u->haars.size() - 1});
   };
   auto add_emb_row = [&](Block& blk, int wp, int bp, int cbp, int n) {
     u->emb_rows_w.push_back(wp); u->emb_rows_b.push_back(bp); u->emb_rows_cb.push_back(cbp);
@@ -273,7 +273,7 @@ void build(cwdm_unet* u) {
       u->tensors[h1].stats_kind = -1;
       u->convs.push_back(c1);
       blk.c1 = (int)u->convs.size() - 1;
-      u->steps.push_back({1, blk.c1});
+      u->steps.push_back({kConv, blk.c1});
       const int row = add_emb_row(blk, c1.emb_w_p, c1.emb_b_p, -1, cout);
       // h: DWT -> LLL / 3 (+ the 7 high bands as the skip) or IDWT(3 h, skip); then + emb
       HaarStep hh{};
@@ -307,7 +307,7 @@ void build(cwdm_unet* u) {
       const int o = c2.out = new_tensor(lout, cout);
       u->convs.push_back(c2);
       blk.c2 = (int)u->convs.size() - 1;
-      u->steps.push_back({1, blk.c2});
+      u->steps.push_back({kConv, blk.c2});
       blk.p_end = (int)u->params.size();
       u->blocks.push_back(blk);
       return o;
@@ -321,7 +321,7 @@ void build(cwdm_unet* u) {
       ps.out_h = new_tensor(lout, cin);
       ps.out_x = new_tensor(lout, cin);
       u->pools.push_back(ps);
-      u->steps.push_back({2, (int)u->pools.size() - 1});
+      u->steps.push_back({kPool, (int)u->pools.size() - 1});
       blk.pool = (int)u->pools.size() - 1;
       a_src = ps.out_h; a_mode = 0; a_gn = -1;
       xres = ps.out_x; xrmode = 0;
@@ -337,7 +337,7 @@ void build(cwdm_unet* u) {
     int h1 = c1.out = new_tensor(lout, cout);
     u->convs.push_back(c1);
     blk.c1 = (int)u->convs.size() - 1;
-    u->steps.push_back({1, (int)u->convs.size() - 1});
+    u->steps.push_back({kConv, (int)u->convs.size() - 1});
 
     int g2 = gn_step(p + ".out_layers.0", h1, -1, lout);
     blk.g2 = g2;
@@ -357,7 +357,7 @@ void build(cwdm_unet* u) {
     c2.bias_kind = 0; c2.cout = cout; c2.level = lout; c2.stats = true;
     int o = c2.out = new_tensor(lout, cout);
     u->convs.push_back(c2);
-    u->steps.push_back({1, (int)u->convs.size() - 1});
+    u->steps.push_back({kConv, (int)u->convs.size() - 1});
     blk.c2 = (int)u->convs.size() - 1;
     blk.p_end = (int)u->params.size();
     u->blocks.push_back(blk);
@@ -380,7 +380,7 @@ void build(cwdm_unet* u) {
     if (down) {
       S2dStep sd{x, new_tensor(lout, 8 * chn), lout, chn};
       u->s2ds.push_back(sd);
-      u->steps.push_back({3, (int)u->s2ds.size() - 1});
+      u->steps.push_back({kS2d, (int)u->s2ds.size() - 1});
       blk.pool = (int)u->s2ds.size() - 1;
       cs.a0 = sd.out; cs.amode = 0; cs.cin_a = 8 * chn; cs.s2 = 1;
     } else {
@@ -388,7 +388,7 @@ void build(cwdm_unet* u) {
     }
     const int o = cs.out = new_tensor(lout, chn);
     u->convs.push_back(cs);
-    u->steps.push_back({1, (int)u->convs.size() - 1});
+    u->steps.push_back({kConv, (int)u->convs.size() - 1});
     blk.c1 = (int)u->convs.size() - 1;
     blk.p_end = (int)u->params.size();
     u->blocks.push_back(blk);
@@ -435,7 +435,7 @@ void build(cwdm_unet* u) {
       cs.bias_kind = 0; cs.res = h; cs.rmode = 0; cs.cout = ch; cs.level = level; cs.stats = true;
       h = pyr = cs.out = new_tensor(level, ch);
       u->convs.push_back(cs);
-      u->steps.push_back({1, (int)u->convs.size() - 1});
+      u->steps.push_back({kConv, (int)u->convs.size() - 1});
       pb.c1 = (int)u->convs.size() - 1;
       pb.p_end = (int)u->params.size();
       u->blocks.push_back(pb);
@@ -513,7 +513,7 @@ void build(cwdm_unet* u) {
         as.out = new_tensor(level, as.channels);
         u->tensors[as.out].stats_kind = 3;
         u->avgs.push_back(as);
-        u->steps.push_back({5, (int)u->avgs.size() - 1});
+        u->steps.push_back({kAvg, (int)u->avgs.size() - 1});
         ch = stack.empty() ? mc : u->tensors[stack.back()].channels;
         h = resblock("output_blocks." + std::to_string(idx) + ".0", as.out, -1, ch, 0);
         u->blocks.back().avg = (int)u->avgs.size() - 1;
@@ -543,7 +543,7 @@ void build(cwdm_unet* u) {
   co.out = -1;
   u->convs.push_back(co);
   u->head_c = (int)u->convs.size() - 1;
-  u->steps.push_back({1, (int)u->convs.size() - 1});
+  u->steps.push_back({kConv, (int)u->convs.size() - 1});
   u->trace.push_back(-1); u->trace_level.push_back(0);
 
   // packed layout
@@ -671,13 +671,13 @@ XsgPlan xsg_plan(const cwdm_unet* u, const ConvStep& cs, const cwdm_conv3d_desc&
   e.b_c0 = e.b_c1 = 0; e.b_w = nullptr;
   if (d.b_w) e.res_mode = 0;
   e.out_dtype = CWDM_F32;
-  SgFp32xScope fx;
-  if (!cwdm::sg_eligible(&e)) return x;
+  // (the forward runs these convs with ConvCall::fp32x set)
+  if (!cwdm::sg_eligible(&e, true)) return x;
   x.e = e;
   x.x3_bytes = align_up(d.B * sv * 3 * C * 2);
   x.skip_bytes = d.b_w ? align_up(d.B * d.D * d.H * d.W * d.cout * 4) : 0;
-  const int S = cwdm::sg_ksplit(&e);
-  int64_t part = S > 1 ? (int64_t)S * d.B * cwdm::ksplit_slice_voxels(&e) * d.cout * 4 : 0;
+  const int S = cwdm::sg_ksplit(&e, true);
+  int64_t part = S > 1 ? (int64_t)S * d.B * cwdm::ksplit_slice_voxels(&e, true) * d.cout * 4 : 0;
   if (d.b_w && cs.xsplit_sk_off >= 0) {
     cwdm_conv3d_desc k = d;
     k.dtype = CWDM_BF16;
@@ -685,12 +685,12 @@ XsgPlan xsg_plan(const cwdm_unet* u, const ConvStep& cs, const cwdm_conv3d_desc&
     k.b_c0 = 3 * (d.b_c0 + d.b_c1); k.b_c1 = 0; k.b1 = nullptr;
     k.bias = nullptr; k.bias_bstride = 0; k.stats = nullptr; k.res = nullptr; k.res_mode = -1;
     k.out_dtype = CWDM_F32;
-    if (cwdm::sg_skip_eligible(&k)) {
+    if (cwdm::sg_skip_eligible(&k, true)) {
       x.sk_sg = true;
       x.ek = k;
       x.x3_bytes = std::max(x.x3_bytes, align_up(d.B * d.D * d.H * d.W * k.b_c0 * 2));
-      const int Sk = cwdm::sg_skip_ksplit(&k);
-      if (Sk > 1) part = std::max(part, (int64_t)Sk * d.B * cwdm::ksplit_slice_voxels(&k) * d.cout * 4);
+      const int Sk = cwdm::sg_skip_ksplit(&k, true);
+      if (Sk > 1) part = std::max(part, (int64_t)Sk * d.B * cwdm::ksplit_slice_voxels(&k, true) * d.cout * 4);
     }
   }
   x.total = x.x3_bytes + x.skip_bytes + part;
@@ -746,7 +746,7 @@ Layout layout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) {
     const auto& c2 = u->convs[c1.skip_conv];
     cwdm_conv3d_desc d1 = conv_shape(u, c1, B, D, H, W), d2 = conv_shape(u, c2, B, D, H, W);
     const int64_t vpb = d1.D * d1.H * d1.W;
-    if (!cwdm::v4_eligible(&d1) || !cwdm::v4_eligible(&d2) ||
+    if (!cwdm::v4_eligible(&d1, cwdm::ConvCall{}) || !cwdm::v4_eligible(&d2, cwdm::ConvCall{}) ||
         !cwdm::apply_skip_ok(u->cfg.dtype, c1.cin_a, c2.cout, B, vpb))
       continue;
     L.skip_fused[i] = 1;
@@ -759,7 +759,7 @@ Layout layout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) {
     const auto& cs = u->convs[i];
     cwdm_conv3d_desc d = conv_shape(u, cs, B, D, H, W);
     if (!dtype_half(u->cfg.dtype) || cs.gn < 0 || cs.amode > 1 || cs.s2 || cwdm::head_eligible(&d) ||
-        !cwdm::v4_eligible(&d))
+        !cwdm::v4_eligible(&d, cwdm::ConvCall{}))
       continue;
     const int64_t sv = cs.amode == 1 ? (d.D / 2) * (d.H / 2) * (d.W / 2) : d.D * d.H * d.W;
     const int64_t cin = d.a_c0 + d.a_c1;
@@ -915,12 +915,6 @@ static int copy_batch_run(cwdm_unet* u, std::vector<CopyJob>& jobs, hipStream_t 
   return CWDM_OK;
 }
 
-// collects every cwdm_conv3d_pack* of its scope into jobs (one launch later)
-struct PackBatchScope {
-  explicit PackBatchScope(std::vector<cwdm::PackJob>* v) { cwdm::g_pack_batch = v; }
-  ~PackBatchScope() { cwdm::g_pack_batch = nullptr; }
-};
-
 // (the packs and the fp32 parameter copies each go out as one batched launch;
 // one launch per parameter / conv cost ~2.5 ms per training step in copies,
 // vec-adds and pack kernels)
@@ -944,30 +938,29 @@ extern "C" int cwdm_unet_pack(const cwdm_unet* uc, const float* const* P, void* 
     cj.push_back(CopyJob{ew + o * u->E, P[u->emb_rows_w[k]], nullptr, n * u->E, 0});
     cj.push_back(CopyJob{eb + o, P[u->emb_rows_b[k]], u->emb_rows_cb[k] < 0 ? nullptr : P[u->emb_rows_cb[k]], n, 0});
   }
+  // the convs' packs, collected for one launch (pack_batch_run below)
   std::vector<cwdm::PackJob> jobs;
+  cwdm::PackJob j;
   int rc;
-  {
-    PackBatchScope scope(&jobs);
-    for (const auto& cs : u->convs) {
-      if (cs.s2) {
-        if ((rc = cwdm_conv3d_pack_s2(P[cs.w_p], cs.cout, cs.cin_a / 8, u->cfg.dtype, base + cs.w_off, 0, stream)))
-          return rc;
-      } else if ((rc = cwdm_conv3d_pack(P[cs.w_p], cs.cout, cs.cin_a, 3, u->cfg.dtype, base + cs.w_off, stream))) {
-        return rc;
-      }
-      if (cs.wphase_off >= 0 &&
-          (rc = cwdm_conv3d_pack_phase(P[cs.w_p], cs.cout, cs.cin_a, u->cfg.dtype, base + cs.wphase_off, stream)))
-        return rc;
-      if (cs.wsplit_off >= 0 &&
-          (rc = cwdm_conv3d_pack_split(P[cs.w_p], cs.cout, cs.cin_a, base + cs.wsplit_off, stream)))
-        return rc;
-      if (cs.ws_p >= 0 &&
-          (rc = cwdm_conv3d_pack(P[cs.ws_p], cs.cout, cs.cin_b, 1, u->cfg.dtype, base + cs.wsk_off, stream)))
-        return rc;
-      if (cs.bias_kind == 0)
-        cj.push_back(CopyJob{reinterpret_cast<float*>(base + cs.bias_off), P[cs.b_p],
-                             cs.wsb_p >= 0 ? P[cs.wsb_p] : nullptr, cs.cout, 0});
+  for (const auto& cs : u->convs) {
+    if ((rc = cs.s2 ? cwdm::pack_s2_job(P[cs.w_p], cs.cout, cs.cin_a / 8, u->cfg.dtype, base + cs.w_off, 0, j)
+                    : cwdm::pack_job(P[cs.w_p], cs.cout, cs.cin_a, 3, u->cfg.dtype, base + cs.w_off, j)))
+      return rc;
+    jobs.push_back(j);
+    if (cs.wphase_off >= 0) {
+      if ((rc = cwdm::pack_phase_job(P[cs.w_p], cs.cout, cs.cin_a, u->cfg.dtype, base + cs.wphase_off, j))) return rc;
+      jobs.push_back(j);
     }
+    if (cs.wsplit_off >= 0 &&
+        (rc = cwdm_conv3d_pack_split(P[cs.w_p], cs.cout, cs.cin_a, base + cs.wsplit_off, stream)))
+      return rc;
+    if (cs.ws_p >= 0) {
+      if ((rc = cwdm::pack_job(P[cs.ws_p], cs.cout, cs.cin_b, 1, u->cfg.dtype, base + cs.wsk_off, j))) return rc;
+      jobs.push_back(j);
+    }
+    if (cs.bias_kind == 0)
+      cj.push_back(CopyJob{reinterpret_cast<float*>(base + cs.bias_off), P[cs.b_p],
+                           cs.wsb_p >= 0 ? P[cs.wsb_p] : nullptr, cs.cout, 0});
   }
   // the accurate fast mode's K-expanded weights (head, small grids): bf16, so packed now, outside the
   // batch (which packs in the model's dtype)
@@ -1028,28 +1021,21 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
   auto* pk = reinterpret_cast<const unsigned char*>(packed);
   auto* wb = reinterpret_cast<unsigned char*>(ws);
   CWDM_HIP(hipMemsetAsync(wb + L.sync, 0, cwdm::plan_sync_bytes(), s));
-  SgSyncScope sync_scope(wb + L.sync);
   float* temb = reinterpret_cast<float*>(wb + L.temb);
   float* ebias = reinterpret_cast<float*>(wb + L.ebias);
   int rc;
-  const float* f = nullptr;
   auto P = [&](int64_t off) { return reinterpret_cast<const float*>(pk + off); };
   if ((rc = launch_time_embed(t, (int)B, u->cfg.model_channels, P(u->off_te_w1), P(u->off_te_b1), P(u->off_te_w2),
                               P(u->off_te_b2), temb, s)))
     return rc;
   if ((rc = launch_emb_proj(temb, (int)B, u->E, P(u->off_emb_w), P(u->off_emb_b), u->R, ebias, s))) return rc;
-  (void)f;
   auto tptr = [&](int id) -> const void* {
     if (id < 0) return nullptr;
     if (id == u->input_tensor) return x;
     return wb + L.t_off[id];
   };
   int conv_i = 0;
-  struct ProfReset {
-    ~ProfReset() { cwdm::g_prof = nullptr; }  // also on an early error return
-  } prof_reset;
   const int es = esize(u->cfg.dtype);
-  (void)es;
   if (u->profiling) {
     const size_t need = u->convs.size() * 4;
     while (u->ev.size() < need) {
@@ -1069,13 +1055,9 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
   // Env CWDM_GNFIN=0: every finalize as its own launch (A/B switch).
   static const bool fin_on = env_not0("CWDM_GNFIN");
   // statistics partial rows per tensor: the per-tile layout, or the rows of a warp-specialised conv
-  // that summed them per workgroup (cwdm::g_stats_rows; env CWDM_STATS_WG=0: per tile everywhere)
-  static const int stats_wg = env_not0("CWDM_STATS_WG");
+  // that summed them per workgroup (ConvCall::stats_rows; env CWDM_STATS_WG=0: per tile everywhere)
+  static const bool stats_wg = env_not0("CWDM_STATS_WG");
   std::vector<int64_t> srows(L.s_parts);
-  struct StatsWgScope {
-    StatsWgScope() { cwdm::g_stats_wg = stats_wg; cwdm::g_stats_rows = 0; }
-    ~StatsWgScope() { cwdm::g_stats_wg = 0; cwdm::g_stats_rows = 0; }
-  } stats_wg_scope;
   int fin_pend = -1;
   auto fin_args = [&](int gi, cwdm::GnFinFuse& f) {
     const auto& g = u->gns[gi];
@@ -1098,9 +1080,9 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
                             f.mr, stream);
   };
   for (const auto& st : u->steps) {
-    if (fin_pend >= 0 && !(st.kind == 1 && u->convs[st.idx].gn == u->gns[fin_pend].ss_id) && (rc = flush_fin()))
+    if (fin_pend >= 0 && !(st.kind == kConv && u->convs[st.idx].gn == u->gns[fin_pend].ss_id) && (rc = flush_fin()))
       return rc;
-    if (st.kind == 2) {
+    if (st.kind == kPool) {
       const auto& ps = u->pools[st.idx];
       const int lv = ps.level_out;
       if ((rc = cwdm_gn_silu_pool(tptr(ps.src), ps.channels, reinterpret_cast<const float*>(wb + L.ss_off[ps.ss_id]),
@@ -1109,7 +1091,7 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
         return rc;
       continue;
     }
-    if (st.kind == 3) {
+    if (st.kind == kS2d) {
       const auto& sd = u->s2ds[st.idx];
       const int lv = sd.level_out;
       if ((rc = cwdm_space_to_depth(tptr(sd.src), sd.channels, B, D >> lv, H >> lv, W >> lv, u->cfg.dtype,
@@ -1117,7 +1099,7 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
         return rc;
       continue;
     }
-    if (st.kind == 4) {
+    if (st.kind == kHaar) {
       const auto& hs = u->haars[st.idx];
       const int lv = hs.level;
       cwdm_haar_nd_desc a{};
@@ -1135,7 +1117,7 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
       if ((rc = cwdm_haar_nd(&a, stream))) return rc;
       continue;
     }
-    if (st.kind == 5) {
+    if (st.kind == kAvg) {
       const auto& as = u->avgs[st.idx];
       const int lv = as.level;
       if ((rc = cwdm_skip_avg(tptr(as.a), tptr(as.b), wb + L.t_off[as.out],
@@ -1144,7 +1126,7 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
         return rc;
       continue;
     }
-    if (st.kind == 0) {
+    if (st.kind == kGn) {
       fin_pend = st.idx;
       if (!fin_on && (rc = flush_fin())) return rc;
       continue;
@@ -1170,7 +1152,11 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
     if (cs.out < 0) { d.out = out; d.out_dtype = CWDM_F32; }
     else { d.out = wb + L.t_off[cs.out]; d.out_dtype = u->cfg.dtype; }
     d.stats = (cs.stats && cs.out >= 0) ? reinterpret_cast<float*>(wb + L.s_off[cs.out]) : nullptr;
-    if (u->profiling) cwdm::g_prof = &u->hooks[conv_i];
+    // this conv's context: the plan's zeroed sync block, per-workgroup statistics, the profiling hook
+    cwdm::ConvCall cc;
+    cc.sync = reinterpret_cast<unsigned*>(wb + L.sync);
+    cc.stats_wg = stats_wg;
+    if (u->profiling) cc.prof = &u->hooks[conv_i];
     // a skip block's conv1 that applies GroupNorm in its own LDS (conv3d_v5,
     // inference) reads x raw: the fused GroupNorm + 1x1-skip pass would only
     // write an activated copy nobody reads; conv2 then runs the 1x1 skip itself
@@ -1178,7 +1164,7 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
       if (!L.skip_fused[ci]) return false;
       if (keep) return true;
       const cwdm_conv3d_desc dc = conv_shape(u, u->convs[ci], B, D, H, W);
-      return !cwdm::v5_eligible(&dc, true);
+      return !cwdm::v5_eligible(&dc, true, cwdm::ConvCall{});
     };
     if (skip_pass_at(st.idx)) {
       // conv1 of a skip block: SiLU(GN1(x)) for this conv and W_skip . x for conv2 in one pass
@@ -1190,7 +1176,7 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
                                     c2.cout, act, wb + L.skipbuf, s)))
         return rc;
       void* part = wb + L.split + ((B * vpb * (d.a_c0 + d.a_c1) * es + 255) & ~(int64_t)255);
-      if ((rc = cwdm::v4_launch(&d, act, d.a_c0 + d.a_c1, nullptr, 0, 1, d.res, d.res_mode, part, s))) return rc;
+      if ((rc = cwdm::v4_launch(&d, act, d.a_c0 + d.a_c1, nullptr, 0, 1, d.res, d.res_mode, part, cc, s))) return rc;
     } else {
       if (cs.ws_p >= 0 && st.idx > 0 && u->convs[st.idx - 1].skip_conv == st.idx && skip_pass_at(st.idx - 1)) {
         // the skip was computed in conv1's GroupNorm pass: a plain residual here
@@ -1200,7 +1186,7 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
       const int64_t x3_bytes = B * d.D * d.H * d.W * 3 * d.a_c0 * 2;
       if (samp && cs.out < 0 && cwdm::head_sampler_eligible(&d, samp)) {
         if ((rc = flush_fin())) return rc;
-        if ((rc = cwdm::head_sampler_forward(&d, samp, s))) return rc;
+        if ((rc = cwdm::head_sampler_forward(&d, samp, cc.prof, s))) return rc;
         if (fused) *fused = 1;
       } else if (cs.hsplit_off >= 0 && !keep && d.a_gn && x3_bytes <= L.split_bytes) {
         // the accurate fast mode's head: a bf16 head over the K-expanded split input (head_split3_prep)
@@ -1214,14 +1200,14 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
         e.a0 = x3; e.a_c0 = 3 * d.a_c0; e.a1 = nullptr; e.a_c1 = 0;
         e.a_gn = nullptr; e.a_w = pk + cs.hsplit_off; e.a_w_split = nullptr;
         e.workspace = nullptr; e.ws_bytes = 0;
-        if ((rc = cwdm_conv3d_forward(&e, stream))) return rc;
+        if ((rc = cwdm::conv3d_forward(&e, cc, s))) return rc;
       } else if (XsgPlan xp = keep ? XsgPlan{} : xsg_plan(u, cs, d); xp.ok && xp.total <= L.split_bytes) {
         // the accurate fast mode on a small grid: one bf16 small-grid conv over the K-expanded split input
         if ((rc = flush_fin())) return rc;
         unsigned char* x3 = wb + L.split;
         const void* res = d.res;
         int rmode = d.res_mode;
-        SgFp32xScope fx;
+        cc.fp32x = true;
         void* part = x3 + xp.x3_bytes + xp.skip_bytes;
         if (d.b_w && xp.sk_sg) {
           // the 1x1 skip first, into an fp32 residual: K-expanded split of the raw input on the small-grid kernel
@@ -1230,8 +1216,8 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
             return rc;
           cwdm_conv3d_desc k = xp.ek;
           k.b0 = x3; k.b_w = pk + cs.xsplit_sk_off;
-          if ((rc = cwdm::sg_skip_launch(&k, x3 + xp.x3_bytes, cwdm::sg_skip_ksplit(&k) > 1 ? part : nullptr, s)))
-            return rc;
+          void* kpart = cwdm::sg_skip_ksplit(&k, cc.fp32x) > 1 ? part : nullptr;
+          if ((rc = cwdm::sg_skip_launch(&k, x3 + xp.x3_bytes, kpart, cc, s))) return rc;
           res = x3 + xp.x3_bytes; rmode = 0;
         } else if (d.b_w) {
           // the 1x1 skip first, into an fp32 residual (pw_split: the split products of the 1x1 weights)
@@ -1240,7 +1226,8 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
           k.bias = nullptr; k.bias_bstride = 0; k.stats = nullptr; k.res = nullptr; k.res_mode = -1;
           k.out = x3 + xp.x3_bytes; k.out_dtype = CWDM_F32;
           k.workspace = nullptr; k.ws_bytes = 0;
-          if ((rc = cwdm::pw_split_eligible(&k) ? cwdm::pw_split_forward(&k, s) : cwdm_conv3d_forward(&k, stream)))
+          if ((rc = cwdm::pw_split_eligible(&k) ? cwdm::pw_split_forward(&k, cc.prof, s)
+                                                : cwdm::conv3d_forward(&k, cc, s)))
             return rc;
           res = k.out; rmode = 0;
         }
@@ -1254,36 +1241,28 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
         e.res = res; e.res_mode = rmode;
         e.out = d.out; e.stats = d.stats;
         e.workspace = nullptr; e.ws_bytes = 0;
-        if ((rc = cwdm::v4_launch(&e, x3, e.a_c0, nullptr, 0, 1, res, rmode, cwdm::sg_ksplit(&e) > 1 ? part : nullptr, s)))
-          return rc;
+        if (cwdm::sg_ksplit(&e, cc.fp32x) <= 1) part = nullptr;
+        if ((rc = cwdm::v4_launch(&e, x3, e.a_c0, nullptr, 0, 1, res, rmode, part, cc, s))) return rc;
       } else {
-        cwdm::ActKeepScope ks(keep && L.keep_off[st.idx] >= 0 ? wb + L.keep_off[st.idx] : nullptr);
+        cc.act_keep = keep && L.keep_off[st.idx] >= 0 ? wb + L.keep_off[st.idx] : nullptr;
         cwdm::GnFinFuse ff{};
         const bool offer = fin_pend >= 0 && d.a_gn == reinterpret_cast<const float*>(wb + L.ss_off[u->gns[fin_pend].ss_id]);
         if (offer) {
           fin_args(fin_pend, ff);
           fin_pend = -1;
-          cwdm::g_gnfin = &ff;
+          cc.gnfin = &ff;
         } else if ((rc = flush_fin())) {
           return rc;
         }
-        rc = cwdm_conv3d_forward(&d, stream);
-        cwdm::g_gnfin = nullptr;
-        if (rc) return rc;
+        if ((rc = cwdm::conv3d_forward(&d, cc, s))) return rc;
         CWDM_REQUIRE(!offer || ff.used, CWDM_E_INVALID,
                      "cwdm_unet_forward: conv " + std::to_string(st.idx) + " did not take its GroupNorm finalize");
-        CWDM_REQUIRE(!ks.ptr || ks.used(), CWDM_E_INVALID,
+        CWDM_REQUIRE(!cc.act_keep || cc.act_kept, CWDM_E_INVALID,
                      "cwdm_unet_forward: conv " + std::to_string(st.idx) + " did not keep its activated input");
       }
     }
-    if (cwdm::g_stats_rows > 0) {
-      if (cs.out >= 0) srows[cs.out] = cwdm::g_stats_rows;
-      cwdm::g_stats_rows = 0;
-    }
-    if (u->profiling) {
-      cwdm::g_prof = nullptr;
-      u->ev_used = conv_i + 1;
-    }
+    if (cc.stats_rows > 0 && cs.out >= 0) srows[cs.out] = cc.stats_rows;
+    if (u->profiling) u->ev_used = conv_i + 1;
     ++conv_i;
   }
   return flush_fin();
@@ -1464,20 +1443,20 @@ extern "C" int cwdm_unet_pack_bwd(const cwdm_unet* uc, const float* const* P, vo
   auto* base = reinterpret_cast<unsigned char*>(packed_bwd);
   int rc;
   std::vector<cwdm::PackJob> jobs;
-  {
-  PackBatchScope scope(&jobs);
+  cwdm::PackJob j;
   for (size_t i = 0; i < u->convs.size(); ++i) {
     const auto& cs = u->convs[i];
-    if (u->dg_off[i] >= 0 && cs.s2 &&
-        (rc = cwdm_conv3d_pack_s2(P[cs.w_p], cs.cout, cs.cin_a / 8, u->cfg.dtype, base + u->dg_off[i], 1, stream)))
-      return rc;
-    if (u->dg_off[i] >= 0 && !cs.s2 &&
-        (rc = cwdm_conv3d_pack_dgrad(P[cs.w_p], cs.cout, cs.cin_a, 3, u->cfg.dtype, base + u->dg_off[i], stream)))
-      return rc;
-    if (u->dgs_off[i] >= 0 &&
-        (rc = cwdm_conv3d_pack_dgrad(P[cs.ws_p], cs.cout, cs.cin_b, 1, u->cfg.dtype, base + u->dgs_off[i], stream)))
-      return rc;
-  }
+    if (u->dg_off[i] >= 0) {
+      if ((rc = cs.s2 ? cwdm::pack_s2_job(P[cs.w_p], cs.cout, cs.cin_a / 8, u->cfg.dtype, base + u->dg_off[i], 1, j)
+                      : cwdm::pack_dgrad_job(P[cs.w_p], cs.cout, cs.cin_a, 3, u->cfg.dtype, base + u->dg_off[i], j)))
+        return rc;
+      jobs.push_back(j);
+    }
+    if (u->dgs_off[i] >= 0) {
+      if ((rc = cwdm::pack_dgrad_job(P[cs.ws_p], cs.cout, cs.cin_b, 1, u->cfg.dtype, base + u->dgs_off[i], j)))
+        return rc;
+      jobs.push_back(j);
+    }
   }
   if ((rc = ensure_table(u->bwd_tab, u->bwd_cap, jobs.size()))) return rc;
   return cwdm::pack_batch_run(jobs, u->cfg.dtype, u->bwd_tab, u->bwd_cache, (hipStream_t)stream);
@@ -1545,7 +1524,7 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
   auto* gb = reinterpret_cast<unsigned char*>(gws);
   // (every call: a caller may run segments on a fresh grad workspace)
   CWDM_HIP(hipMemsetAsync(gb + G.sync, 0, cwdm::plan_sync_bytes(), s));
-  SgSyncScope sync_scope(gb + G.sync);
+  unsigned* const sync = reinterpret_cast<unsigned*>(gb + G.sync);
   auto P = [&](int64_t off) { return reinterpret_cast<const float*>(pk + off); };
   auto GR = [&](int pi) { return grads + u->goff[pi]; };
   auto act = [&](int id) -> const void* {
@@ -1595,14 +1574,17 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
     d.ws_bytes = G.wgws_bytes;
     return cwdm_conv3d_wgrad(&d, stream);
   };
-  auto dgrad = [&](int ci, const void* dy) -> int {
+  auto dgrad = [&](int ci, const void* dy, cwdm::GbwdFuse* gbwd = nullptr) -> int {
     cwdm_conv3d_desc d = dgrad_shape(u, ci, B, D, H, W);
     d.a0 = dy;
     d.a_w = pb + u->dg_off[ci];
     d.out = tmp;
     d.workspace = gb + G.split;
     d.ws_bytes = G.split_bytes;
-    return cwdm_conv3d_forward(&d, stream);
+    cwdm::ConvCall cc;
+    cc.sync = sync;
+    cc.gbwd = gbwd;
+    return cwdm::conv3d_forward(&d, cc, s);
   };
   // dgrad conv ci whose output du (tmp) feeds the SiLU(GroupNorm gi) backward at
   // the same grid, input x = (xid0, xid1): the conv's epilogue takes the reduce
@@ -1620,9 +1602,7 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
     f.ss = ss_of(gi); f.mr = mr_of(gi); f.groups = u->cfg.num_groups;
     f.part = gbp;
     f.part_bytes = G.gbp_bytes - align_up(B * (int64_t)kGbSlices * g.channels * 8);
-    cwdm::g_gbwd = &f;
-    const int r = dgrad(ci, dy);
-    cwdm::g_gbwd = nullptr;
+    const int r = dgrad(ci, dy, &f);
     if (r || !f.used) return r;
     if (f.nblk <= 512) {   // few tiles: gn_bwd_finalize reads them directly
       pre.part = gbp; pre.nblk = f.nblk;
@@ -1843,10 +1823,10 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
         }
         d.accumulate = a0;
         d.workspace = gb + G.split; d.ws_bytes = G.split_bytes;
-        cwdm::g_gapply = gf;
-        const int r = cwdm_conv3d_forward(&d, stream);
-        cwdm::g_gapply = nullptr;
-        if (r) return r;
+        cwdm::ConvCall cc;
+        cc.sync = sync;
+        cc.gapply = gf;
+        if (int r = cwdm::conv3d_forward(&d, cc, s)) return r;
         CWDM_REQUIRE(!gf || gf->used, CWDM_E_UNSUPPORTED, "train plan: skip dgrad did not take the fused apply");
         return CWDM_OK;
       };

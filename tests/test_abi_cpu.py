@@ -191,3 +191,21 @@ def test_environment_is_read_only_through_the_knob_helpers():
     users = sorted(f for f in os.listdir(csrc)
                    if f.endswith((".hip", ".cpp", ".hpp", ".h")) and "getenv(" in open(os.path.join(csrc, f)).read())
     assert users == ["common.hpp"], users
+
+
+def test_per_thread_state_is_the_error_channel_and_one_debug_hook():
+    """What a conv call takes and reports beyond its desc travels in a ConvCall
+    (internal.hpp), not in per-thread globals: the only thread_local variables
+    under csrc are the error channel and the state behind cwdm_debug_stats_wg,
+    each local to its file (none declared extern or inline for another unit)."""
+    csrc = os.path.join(ROOT, "fast-cwdm_amd", "csrc")
+    found = set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".cpp", ".hpp", ".h")):
+            continue
+        text = open(os.path.join(csrc, f)).read()
+        assert "extern thread_local" not in text and "inline thread_local" not in text, f
+        code = re.sub(r"//[^\n]*|/\*.*?\*/", "", text, flags=re.S)
+        for decl in re.findall(r"\bthread_local\b([^;]*);", code):
+            found.add((f, re.match(r"[^=({]*?(\w+)\s*(?:[=({]|$)", decl.strip()).group(1)))
+    assert found == {("api.cpp", "g_err"), ("conv3d.hip", "t_stats_wg"), ("conv3d.hip", "t_stats_rows")}, found

@@ -1,5 +1,6 @@
 """End-to-end parity on the GPU: native UNetModel forward, the sampling loop
 and training_losses against the oracle (fp32 within 1e-3 rel)."""
+import math
 import os
 
 import numpy as np
@@ -536,3 +537,71 @@ def test_fast_ddpm_sampled10_production_loop_vs_oracle():
     tab = od.Tables(od.beta_schedule("linear", 10, "sampled"))
     ref = od.p_sample_loop(tab, ou.OracleUNet(P, num_groups=8, **cases.C1_CFG), x_T, cond, noises)
     assert rel_err(out, ref) < 1e-3
+
+
+def _lone_conv_with_stats(src, packed, bias):
+    """A lone 64 -> 64 3x3x3 bf16 cwdm_conv3d_forward with statistics on src (1, D, H, W, 64);
+    returns (out, statistics rows)."""
+    import ctypes
+    from cwdm_hip import _lib
+    from cwdm_hip._lib import check, lib
+    L = lib()
+    _, D, H, W, C = src.shape
+    out = torch.empty(1, D, H, W, 64, device=DEV, dtype=torch.bfloat16)
+    st = torch.zeros(1, L.cwdm_conv3d_parts(_lib.CWDM_BF16, D, H, W, 64), 64, 2, device=DEV)
+    d = _lib.ConvDesc()
+    d.dtype, d.B, d.D, d.H, d.W, d.cout = _lib.CWDM_BF16, 1, D, H, W, 64
+    d.a0, d.a_c0, d.a_w = src.data_ptr(), C, packed.data_ptr()
+    d.bias, d.res_mode = bias.data_ptr(), -1
+    d.out, d.out_dtype, d.stats = out.data_ptr(), _lib.CWDM_BF16, st.data_ptr()
+    nws = L.cwdm_conv3d_workspace_bytes(ctypes.byref(d))
+    ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=DEV)
+    d.workspace, d.ws_bytes = ws.data_ptr(), nws
+    check(L.cwdm_conv3d_forward(ctypes.byref(d), None))
+    torch.cuda.synchronize()
+    return out, st
+
+
+def test_plan_leaves_lone_convs_and_the_stats_wg_hook_alone():
+    """A plan forward + backward hands its convs their context explicitly, so nothing of it stays
+    behind on the calling thread: a lone conv on the warp-specialised kernel (W = its minimum width,
+    one tile per CU) gives the same output and statistics before and after, and a
+    cwdm_debug_stats_wg(1) set before the plan runs is still set afterwards, with -1 reporting the
+    lone conv's own rows."""
+    import ctypes
+    from cwdm_hip import _lib
+    from cwdm_hip._lib import check, lib
+    L = lib()
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    k = math.isqrt(ncu - 1) + 1                      # k * k >= ncu tiles of 32 x 4 x 4 (CWDM_V5_MIN_TPC = 1)
+    g = torch.Generator().manual_seed(61)
+    src = torch.randn(1, 4 * k, 4 * k, 24, 64, generator=g).to(DEV, torch.bfloat16)
+    w = (torch.randn(64, 64, 3, 3, 3, generator=g) / math.sqrt(27 * 64)).to(DEV)
+    bias = (0.1 * torch.randn(64, generator=g)).to(DEV)
+    packed = torch.empty(L.cwdm_conv3d_packed_bytes(64, 64, 3, _lib.CWDM_BF16), dtype=torch.uint8, device=DEV)
+    check(L.cwdm_conv3d_pack(ctypes.c_void_p(w.data_ptr()), 64, 64, 3, _lib.CWDM_BF16,
+                             ctypes.c_void_p(packed.data_ptr()), None))
+    cfg, G = cases.C1_CFG, cases.C1_GROUPS
+    model = _product_model(cfg, G, ou.random_params(seed=1, **cfg), "bf16")
+    x = torch.randn(1, 32, 16, 16, 16, generator=g).to(DEV)
+    t = torch.tensor([300], device=DEV)
+
+    def plan_step():
+        model.zero_grad(set_to_none=True)
+        model(x, t).float().square().sum().backward()
+        torch.cuda.synchronize()
+
+    for wg in (0, 1):
+        prev = L.cwdm_debug_stats_wg(wg)
+        try:
+            out0, st0 = _lone_conv_with_stats(src, packed, bias)
+            rows0 = L.cwdm_debug_stats_wg(-1)
+            assert rows0 == (min(ncu, k * k) if wg else 0)   # one row per workgroup, one workgroup per CU
+            assert bool(st0[0, rows0:].any()) == (not wg)    # (per workgroup: the rows past the grid untouched)
+            plan_step()
+            assert L.cwdm_debug_stats_wg(wg) == wg           # still set (and the rows count starts over)
+            out1, st1 = _lone_conv_with_stats(src, packed, bias)
+            assert L.cwdm_debug_stats_wg(-1) == rows0
+            assert torch.equal(out1, out0) and torch.equal(st1, st0)
+        finally:
+            L.cwdm_debug_stats_wg(prev)
