@@ -184,6 +184,12 @@ __device__ __forceinline__ void v4_read_step(u32x4 (&av)[6], const unsigned char
   for (int L = 0; L < 6; ++L)
     av[L] = *reinterpret_cast<const u32x4*>(hb + (((PL + 1 + DZ) * V4Cfg::HY + L) * V4Cfg::HX + (DX + 1)) * 16);
 }
+// line L of those six alone (conv3d_v5.hip spreads a step's reads over the previous step's MFMA gaps)
+template <int K, int L>
+__device__ __forceinline__ void v4_read_line(u32x4& a, const unsigned char* hb) {
+  constexpr int G = K / 2, PL = K % 2, DZ = G / 3 - 1, DX = G % 3 - 1;
+  a = *reinterpret_cast<const u32x4*>(hb + (((PL + 1 + DZ) * V4Cfg::HY + L) * V4Cfg::HX + (DX + 1)) * 16);
+}
 
 // Epilogue of one output tile from the accumulator registers: + residual,
 // store (or accumulate), per-channel (sum, sum^2) partials for the next

@@ -10,11 +10,12 @@
 // (r02, DESIGN.md §3: the halo is 2.4x the tile and the SIMDs are MFMA-bound).
 //
 // Design (MI355X / gfx950), one 512-thread workgroup per CU, persistent:
-//   * waves 0-3 ("MFMA waves", s_setprio 2) run exactly v4's MFMA schedule on
+//   * waves 0-3 ("MFMA waves", s_setprio 2) run exactly v4's MFMA order on
 //     a 32(x) x 4(y) x 4(z) x 64-channel tile: 8 accumulators of 32 ch x 32 vox
 //     per wave, 216 v_mfma_f32_32x32x16 per 16-channel chunk, weights straight
-//     to VGPRs two groups ahead.  They issue no halo DMA, no VALU epilogue and
-//     no global store;
+//     to VGPRs two groups ahead; the next step's LDS operand reads and the
+//     weight loads go out one per MFMA gap (V5_STEP).  They issue no halo DMA,
+//     no VALU epilogue and no global store;
 //   * waves 4-7 ("helper waves", one per SIMD beside an MFMA wave) own the
 //     data movement: per chunk k they issue the halo DMA of chunk k + 2 (and
 //     the chunk's 16 GroupNorm (scale, shift) pairs), wait for their OWN pieces
@@ -328,6 +329,11 @@ __global__ void __launch_bounds__(512) conv3d_v5_kernel(V4Params p) {
       v4_gload(w[1], src + 3 * 2048);
       v4_gload(w[2], src + 6 * 2048);
     };
+    // tap dy of that group alone (the chunk loop issues each in an MFMA gap of its own)
+    auto load_w1 = [&](u32x4& w, int ct, int c, int g, int dy) {
+      if (V5_DIAG(4)) return;
+      v4_gload(w, wlane + ((long long)ct * p.nch + c) * 27 * 2048 + ((g / 3) * 9 + (g % 3) + 3 * dy) * 2048);
+    };
     // phase instance: group g = (tz, tx) = taps 4 tz + tx (ty 0) and + 2 (ty 1) of the tile's phase
     auto load_wp = [&](u32x4 (&w)[3], const V4Tile& t, int c, int g) {
       if (V5_DIAG(4)) return;
@@ -396,30 +402,51 @@ __global__ void __launch_bounds__(512) conv3d_v5_kernel(V4Params p) {
         } else {
         const unsigned char* hb = smem + (gch % 3) * C::HALO_B + hlane;
         if (!V5_DIAG(2)) v4_read_step<0>(av[0], hb);
+        /* One step = 12 MFMAs of one (dz, dx) group on one plane.  Its gaps carry the memory ops, at most one  */
+        /* ds_read_b128 and one global_load_dwordx4 each (three 16-B LDS reads in one gap saturate the CU's    */
+        /* LDS array and stretch the gap; two cost ~3 cycles): line I / 2 of step K + 1 behind MFMA I = 0, 2,  */
+        /* .. 10, and on even steps weight tap I / 2 of group GI + 2 behind MFMA I = 1, 3, 5.  Every op is     */
+        /* pinned by sched_barrier(0); the compiler counts the lgkmcnt of the LDS reads itself.                */
+        /* Weights: straight-line loads and counted waits only: a runtime branch between an asm load and its   */
+        /* wait lets the register allocator copy the destination before the data lands (the last tile reloads  */
+        /* its own first group instead of skipping the load: nxt == cur there).  They run two groups ahead     */
+        /* (one MFMA wave per SIMD: nothing else hides an L2 round trip).  An even step opens with the wait    */
+        /* for its own group GI: in flight there are the 3 loads of GI (issued in step K - 4) and the 3 of     */
+        /* GI + 1 (step K - 2), so vmcnt(3) retires GI and leaves GI + 1; GI + 2 goes out behind the wait into */
+        /* the slot of GI - 1, whose last MFMA issued in step K - 1.  Groups 9 and 10 are groups 0 and 1 of    */
+        /* the next chunk, or of the next tile's first chunk (LAST: nxt), issued in steps 14 and 16, so step 0 */
+        /* of every chunk finds the same two groups in flight as step 0 of the first (loaded before B0).       */
+#define V5_LOAD_W(J)                                                                                         \
+          if (GI + 2 < 9) load_w1(wr[(GI + 2) % 3][J], cur.ct, V5_PHYS(cur, c), GI + 2, J);                  \
+          else if (!LAST) load_w1(wr[(GI + 2) % 3][J], cur.ct, V5_PHYS(cur, c + 1), GI - 7, J);              \
+          else load_w1(wr[(GI + 2) % 3][J], nxt.ct, V5_PHYS(nxt, nxt.c0), GI - 7, J);
+#define V5_MFMA(K, I)                                                                                        \
+        {                                                                                                    \
+          constexpr int GI = (K) / 2, PL = (K) % 2, KN = (K) + 1, BC = (K) & 1, DY = (I) / 4, M = (I) % 4;   \
+          v4_mfma<T>(acc[PL][M], wr[GI % 3][DY], av[BC][M + DY]);                                            \
+          __builtin_amdgcn_sched_barrier(0);                                                                 \
+          if ((I) % 2 == 0 && KN < 18) {                                                                     \
+            if (!V5_DIAG(2)) v4_read_line<KN % 18, (I) / 2>(av[BC ^ 1][(I) / 2], hb);                        \
+            __builtin_amdgcn_sched_barrier(0);                                                               \
+          }                                                                                                  \
+          if ((I) % 2 == 1 && (I) < 6 && PL == 0) {                                                          \
+            V5_LOAD_W((I) / 2)                                                                               \
+            __builtin_amdgcn_sched_barrier(0);                                                               \
+          }                                                                                                  \
+        }
 #define V5_STEP(K)                                                                                           \
         {                                                                                                    \
-          constexpr int GI = (K) / 2, PL = (K) % 2, KN = (K) + 1, BC = (K) & 1;                              \
-          /* straight-line loads and counted waits only: a runtime branch between an asm load and its  */ \
-          /* wait lets the register allocator copy the destination before the data lands (the last tile */ \
-          /* reloads its own first group instead of skipping the load: nxt == cur there)               */ \
-          /* weights two groups ahead (one MFMA wave per SIMD: nothing else hides an L2 round trip) */   \
-          if (PL == 0) {                                                                                     \
-            if (GI + 2 < 9) load_w(wr[(GI + 2) % 3], cur.ct, V5_PHYS(cur, c), GI + 2);                       \
-            else if (!LAST) load_w(wr[(GI + 2) % 3], cur.ct, V5_PHYS(cur, c + 1), GI - 7);                   \
-            else load_w(wr[(GI + 2) % 3], nxt.ct, V5_PHYS(nxt, nxt.c0), GI - 7);                             \
-          }                                                                                                  \
-          if (KN < 18 && !V5_DIAG(2)) v4_read_step<KN % 18>(av[BC ^ 1], hb);                                 \
-          if (PL == 0) V4_WAIT_W(6, wr[GI % 3]);                                                             \
+          if ((K) % 2 == 0) V4_WAIT_W(3, wr[((K) / 2) % 3]);                                                 \
           __builtin_amdgcn_sched_barrier(0);                                                                 \
-          _Pragma("unroll") for (int dy = 0; dy < 3; ++dy)                                                   \
-          _Pragma("unroll") for (int m = 0; m < 4; ++m)                                                      \
-            v4_mfma<T>(acc[PL][m], wr[GI % 3][dy], av[BC][m + dy]);                                          \
-          __builtin_amdgcn_sched_barrier(0);                                                                 \
+          V5_MFMA(K, 0) V5_MFMA(K, 1) V5_MFMA(K, 2) V5_MFMA(K, 3) V5_MFMA(K, 4) V5_MFMA(K, 5)                \
+          V5_MFMA(K, 6) V5_MFMA(K, 7) V5_MFMA(K, 8) V5_MFMA(K, 9) V5_MFMA(K, 10) V5_MFMA(K, 11)              \
         }
         V5_STEP(0) V5_STEP(1) V5_STEP(2) V5_STEP(3) V5_STEP(4) V5_STEP(5)
         V5_STEP(6) V5_STEP(7) V5_STEP(8) V5_STEP(9) V5_STEP(10) V5_STEP(11)
         V5_STEP(12) V5_STEP(13) V5_STEP(14) V5_STEP(15) V5_STEP(16) V5_STEP(17)
 #undef V5_STEP
+#undef V5_MFMA
+#undef V5_LOAD_W
         }
         V5_STAMP(2 + gch, tid == 0 && gch < 16);
         __builtin_amdgcn_s_barrier();   // chunk k read; chunk k + 1 transformed
@@ -453,7 +480,8 @@ __global__ void __launch_bounds__(512) conv3d_v5_kernel(V4Params p) {
       __builtin_amdgcn_s_barrier();   // B2: tile staged
       cur = nxt;
     }
-    // the dummy reloads of the last tile
+    // the dummy reloads of the last tile (its last chunk's groups "9" and "10" into slots 0 and 1: the
+    // only loads still in flight; vmcnt(0) leaves none)
     if constexpr (PH) {
       asm volatile("s_waitcnt vmcnt(0)" : "+v"(wr[0][0]), "+v"(wr[0][1]), "+v"(wr[1][0]), "+v"(wr[1][1])::"memory");
     } else {
