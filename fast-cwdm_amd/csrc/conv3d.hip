@@ -476,10 +476,11 @@ Plan1 plan_conv(const cwdm_conv3d_desc* d) {
 
 extern "C" int64_t cwdm_conv3d_workspace_bytes(const cwdm_conv3d_desc* d) {
   if (!d || d->B <= 0 || d->D <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0) return -1;
-  const int64_t legacy = plan_conv(d).ws;
-  const ConvCall c;
-  return (v4_eligible(d, c) || (d->a_w_split && v5_eligible(d, false, c))) ? std::max(legacy, v4_workspace_bytes(d, c))
-                                                                           : legacy;
+  return conv_workspace_bytes(d, conv_route(d, ConvCall{}));
+}
+
+int64_t cwdm::conv_workspace_bytes(const cwdm_conv3d_desc* d, const ConvRoute& r) {
+  return std::max(plan_conv(d).ws, r.ws_total);
 }
 
 extern "C" int64_t cwdm_conv3d_parts(int dtype, int64_t D, int64_t H, int64_t W, int cout) {
@@ -509,6 +510,17 @@ extern "C" int cwdm_conv3d_forward(const cwdm_conv3d_desc* d, cwdm_stream_t stre
   return rc;
 }
 
+// the route of (d, c) with the workspace d brings: the preferred one, or the brick kernels below its size
+static ConvRoute effective_route(const cwdm_conv3d_desc* d, const ConvCall& c) {
+  ConvRoute r = conv_route(d, c);
+  if (r.ws_total > 0 && !(d->workspace && d->ws_bytes >= r.ws_total)) {
+    const bool fin = r.flush_fin || r.gn == GnInput::FinApply;
+    r = ConvRoute{};
+    r.flush_fin = fin;
+  }
+  return r;
+}
+
 int cwdm::conv3d_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s) {
   CWDM_REQUIRE(d && d->out && (d->a_w || d->b_w), CWDM_E_INVALID, "cwdm_conv3d_forward: null pointer");
   CWDM_REQUIRE(!d->a_w || (d->a0 && d->a_c0 > 0), CWDM_E_INVALID, "cwdm_conv3d_forward: segment A input missing");
@@ -529,24 +541,30 @@ int cwdm::conv3d_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s) 
   CWDM_REQUIRE(d->res_mode < 0 || d->res, CWDM_E_INVALID, "cwdm_conv3d_forward: residual pointer missing");
   CWDM_REQUIRE(d->out_dtype == CWDM_F32 || d->out_dtype == d->dtype, CWDM_E_INVALID,
                "cwdm_conv3d_forward: output dtype must be fp32 or the compute dtype");
-  // (an offered GroupNorm finalize, GnFinFuse, runs first on every route but the
-  // DMA-staged one, whose pre-pass may take it)
-  int rc;
-  if (head_eligible(d)) {
-    if ((rc = gnfin_flush(d, c.gnfin, s))) return rc;
-    return head_conv_forward(d, c.prof, s);
+  const ConvRoute r = effective_route(d, c);
+  if (r.flush_fin)
+    if (int rc = gnfin_flush(d, c.gnfin, s)) return rc;
+  switch (r.kernel) {
+    case ConvKernel::Head: return head_conv_forward(d, c.prof, s);
+    case ConvKernel::Pointwise: return pw_forward(d, c, r.takes_gapply, s);
+    case ConvKernel::Brick: return legacy_conv3d_forward(d, c.prof, s);
+    default: return conv3d_v4_forward(d, r, c, s);
   }
-  if (pw_eligible(d)) {
-    if ((rc = gnfin_flush(d, c.gnfin, s))) return rc;
-    return pw_forward(d, c, s);
-  }
-  // (the accurate fast mode's split-bf16 kernel takes fp32 shapes of any size: the same host path)
-  if (v4_eligible(d, c) || (d->a_w_split && v5_eligible(d, false, c))) {
-    const int64_t need = v4_workspace_bytes(d, c);
-    if (need == 0 || (d->workspace && d->ws_bytes >= need)) return conv3d_v4_forward(d, c, s);
-  }
-  if ((rc = gnfin_flush(d, c.gnfin, s))) return rc;
-  return legacy_conv3d_forward(d, c.prof, s);
+}
+
+// diagnostics / tests: the route a lone cwdm_conv3d_forward(d) takes (pointers as presence flags:
+// nothing is read through them, no device call but the CU-count and occupancy queries)
+extern "C" int cwdm_debug_conv_route(const cwdm_conv3d_desc* d, int* out, int n) {
+  CWDM_REQUIRE(d && out && n >= 6, CWDM_E_INVALID, "cwdm_debug_conv_route: null pointer or fewer than 6 slots");
+  CWDM_REQUIRE(d->B > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->cout > 0, CWDM_E_SHAPE,
+               "cwdm_debug_conv_route: empty shape");
+  CWDM_REQUIRE(dtype_compute(d->dtype), CWDM_E_INVALID, "cwdm_debug_conv_route: bad dtype");
+  ConvCall c;
+  c.stats_wg = t_stats_wg != 0;
+  const ConvRoute r = effective_route(d, c);
+  out[0] = (int)r.kernel; out[1] = (int)r.gn; out[2] = (int)r.skip;
+  out[3] = r.ksplit; out[4] = r.aa_units; out[5] = (int)std::min<int64_t>(r.ws_total, 0x7FFFFFFF);
+  return CWDM_OK;
 }
 
 // the brick / split-K kernels of conv3d_kernels.hpp (every shape and mode)

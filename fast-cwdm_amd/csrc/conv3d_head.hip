@@ -666,12 +666,7 @@ bool head_eligible(const cwdm_conv3d_desc* d) {
 
 namespace {
 Head2Geo head2_geo(const HeadParams& p, int& grid) {
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return 256;
-    return n > 0 ? n : 256;
-  }();
+  const int ncu = cu_count();
   Head2Geo g{};
   g.cx = p.W / 16; g.cy = p.H / 4; g.ntz = p.D / 4;
   const long long cols = (long long)p.B * g.cx * g.cy;

@@ -2,7 +2,7 @@
 // W = 16 or 8), bf16 or fp16, on v_mfma_f32_16x16x32_{bf16,f16}.  Same contract as the
 // DMA-staged wide-grid kernel (V4Params: GroupNorm+SiLU and the 1x1 skip are
 // pre-passes in conv3d_v4_forward; this kernel stages raw copies), called from
-// v4_launch for shapes sg_eligible() accepts.
+// v4_launch for the shapes conv_route gives it (conv_route.cpp: sg_eligible).
 //
 // Why a separate kernel: a 16^3 x 256-channel conv is only 4096 x 256 outputs.
 // The wide kernel's 512-voxel x 64-channel tiles give 32 work items there, so
@@ -446,18 +446,7 @@ template __global__ void conv3d_sg_kernel<f16_t, 8, 8, 0, 27>(SGParams);
 template __global__ void conv3d_sg_kernel<f16_t, 8, 8, 1, 27>(SGParams);
 template __global__ void conv3d_sg_kernel<f16_t, 8, 8, 0, 1>(SGParams);
 
-// fp32x (ConvCall::fp32x, set by the U-Net plan for the accurate fast mode's K-expanded small-grid
-// convs): a 16-bit conv with fp32 output takes this kernel, its residual fp32 too
 namespace {
-bool sg_shape_ok(const cwdm_conv3d_desc* d, bool fp32x) {
-  if (g_conv_path.load(std::memory_order_relaxed) == 1) return false;
-  if (!dtype_half(d->dtype) || d->accumulate || d->out1 || d->cout % 64) return false;
-  if (d->out_dtype != d->dtype && !(d->out_dtype == CWDM_F32 && fp32x)) return false;
-  // W < kWideMinW (the wide kernels take the rest): 16 x 4 x 4 bricks for W >= 16,
-  // 8 x 8 x 4 below (pick_brick's statistics bricks), the last brick of an axis partial
-  return d->W >= 1 && d->W < kWideMinW && d->H >= 1 && d->D >= 1;
-}
-
 // statistics bricks of a small grid: (bx, tx, ty, tz), parts = tx ty tz (== cwdm_conv3d_parts)
 struct SgGeom { int bx, tx, ty, tz; int64_t parts() const { return (int64_t)tx * ty * tz; } };
 SgGeom sg_geom(const cwdm_conv3d_desc* d) {
@@ -465,63 +454,6 @@ SgGeom sg_geom(const cwdm_conv3d_desc* d) {
   return SgGeom{bx, (int)ceil_div(d->W, bx), (int)ceil_div(d->H, by), (int)ceil_div(d->D, 4)};
 }
 }  // namespace
-
-// shapes the small-grid kernel takes: bf16, plain bf16 output (no fp32 / dual /
-// accumulating output), same-grid or upsampled source and residual, W = 16
-// (16x4x4 statistics bricks) or W = 8 (8x8x4), 32-channel K chunks.  At 8^3
-// there are only 32 tiles: K split across workgroups (sg_ksplit), finished by
-// the last slice of each tile.
-bool sg_eligible(const cwdm_conv3d_desc* d, bool fp32x) {
-  if (!sg_shape_ok(d, fp32x) || !d->a_w) return false;
-  if (d->a_mode != 0 && d->a_mode != 1) return false;
-  if (d->res_mode < -1 || d->res_mode > 1) return false;
-  if ((d->a_c0 + d->a_c1) % 32 || d->a_c0 % 16) return false;
-  const int64_t V = d->D * d->H * d->W;
-  const int64_t SV = d->a_mode == 1 ? V / 8 : V;
-  return SV * (d->a_c0 + d->a_c1) * 2 < 0xFFFFE000LL && d->B * (V / 256) * (d->cout / 16) < (1LL << 31);
-}
-
-// the 1x1 skip segment alone (segment B of a desc, channels-last sources)
-bool sg_skip_eligible(const cwdm_conv3d_desc* d, bool fp32x) {
-  if (!sg_shape_ok(d, fp32x) || !d->b_w) return false;
-  if ((d->b_c0 + d->b_c1) % 32 || d->b_c0 % 16) return false;
-  const int64_t V = d->D * d->H * d->W;
-  return V * (d->b_c0 + d->b_c1) * 2 < 0xFFFFE000LL && d->B * (V / 256) * (d->cout / 16) < (1LL << 31);
-}
-
-// K slices of a launch: enough work items for the chip (~256), at least one
-// 32-channel chunk per slice (the 16^3 level has 256 tiles: no split)
-namespace {
-int sg_split_for(const cwdm_conv3d_desc* d, int cin, bool skip = false) {
-  const int64_t parts = sg_geom(d).parts();
-  const int64_t tiles = d->B * parts * (d->cout / 16);
-  const int nch = cin / 32;
-  // work-item target (env CWDM_SG_TARGET, A/B knob; 192 since r04: the 8^3
-  // level splits K 4 ways instead of 8, 66.28 -> 66.54 steps/s on one box,
-  // config 5 unchanged -- profiles/r04/g_sg_target_ab.txt); the 1x1 skips' own
-  // (env CWDM_SG_SKIP_TARGET, A/B knob, default the same)
-  static const int64_t target3 = env_ll("CWDM_SG_TARGET", 192);
-  static const int64_t target1 = env_ll("CWDM_SG_SKIP_TARGET", target3);
-  const int64_t target = skip ? target1 : target3;
-  if (tiles >= target || nch < 2) return 1;
-  int S = (int)std::min<int64_t>((target + tiles - 1) / tiles, nch);
-  const int per = (nch + S - 1) / S;
-  S = (nch + per - 1) / per;
-  return (tiles * S < (1 << 16) && S > 1) ? S : 1;
-}
-}  // namespace
-
-int sg_ksplit(const cwdm_conv3d_desc* d, bool fp32x) {
-  return sg_eligible(d, fp32x) ? sg_split_for(d, d->a_c0 + d->a_c1) : 1;
-}
-// voxels per batch of one K-split slice: the small-grid kernel stores whole
-// (possibly partial) bricks of 256 voxels, the wide kernel the grid itself
-int64_t ksplit_slice_voxels(const cwdm_conv3d_desc* d, bool fp32x) {
-  return sg_shape_ok(d, fp32x) ? sg_geom(d).parts() * 256 : d->D * d->H * d->W;
-}
-int sg_skip_ksplit(const cwdm_conv3d_desc* d, bool fp32x) {
-  return sg_skip_eligible(d, fp32x) ? sg_split_for(d, d->b_c0 + d->b_c1, true) : 1;
-}
 
 // bytes of the K-split counter block a lone launch keeps behind its slices (0 without a split)
 int64_t sg_sync_bytes(int ksplit) { return ksplit > 1 ? kSgSyncWords * 4 : 0; }
@@ -587,30 +519,33 @@ int sg_go(const SGParams& q0, const cwdm_conv3d_desc* d, int taps, double flops,
 }
 }  // namespace
 
-// partial: fp32 scratch of sg_ksplit(d, c.fp32x) x B x V x cout (the K-split slices) followed
-// by sg_sync_bytes of counters, else unused
-int sg_launch(const V4Params& v, const cwdm_conv3d_desc* d, void* partial, const ConvCall& c, hipStream_t s) {
+// ksplit: the route's (ConvRoute::ksplit); partial: fp32 scratch of ksplit x B x (256-voxel bricks) x cout
+// (the K-split slices) followed by sg_sync_bytes of counters, else unused
+int sg_launch(const V4Params& v, const cwdm_conv3d_desc* d, int ksplit, void* partial, const ConvCall& c,
+              hipStream_t s) {
   SGParams q{};
   q.v = v;
   q.ntile16 = d->cout / 16;
   const SgGeom gm = sg_geom(d);
   q.parts = (int)gm.parts();
   q.tx = gm.tx; q.ty = gm.ty;
-  q.ksplit = sg_ksplit(d, c.fp32x);
+  q.ksplit = ksplit;
   q.kper = ((d->a_c0 + d->a_c1) / 32 + q.ksplit - 1) / q.ksplit;
   q.part = reinterpret_cast<float*>(partial);
   CWDM_REQUIRE(q.ksplit == 1 || partial, CWDM_E_INVALID, "conv3d (small grid): K-split scratch missing");
   int rc;
   if ((rc = sg_counters(q, c.sync, q.ksplit > 1 ? reinterpret_cast<unsigned char*>(partial) +
-                                                      (int64_t)q.ksplit * d->B * ksplit_slice_voxels(d, c.fp32x) * d->cout * 4
+                                                      (int64_t)q.ksplit * d->B * q.parts * 256 * d->cout * 4
                                                 : nullptr, s)))
     return rc;
   return sg_go(q, d, 27, 2.0 * d->B * d->D * d->H * d->W * (double)d->cout * 27.0 * (d->a_c0 + d->a_c1), c.prof, s);
 }
 
 // out = W_skip . [b0 | b1] (bf16, no bias / residual / statistics): the skip
-// pre-pass of conv3d_v4_forward; partial: fp32 scratch of sg_skip_ksplit(d, c.fp32x) x B x V x cout
-int sg_skip_launch(const cwdm_conv3d_desc* d, void* out, void* partial, const ConvCall& c, hipStream_t s) {
+// pre-pass of conv3d_v4_forward; ksplit: the route's (ConvRoute::skip_ksplit); partial: fp32 scratch
+// of ksplit x B x (256-voxel bricks) x cout
+int sg_skip_launch(const cwdm_conv3d_desc* d, void* out, void* partial, int ksplit, const ConvCall& c,
+                   hipStream_t s) {
   SGParams q{};
   V4Params& p = q.v;
   const int64_t V = d->D * d->H * d->W;
@@ -624,18 +559,18 @@ int sg_skip_launch(const cwdm_conv3d_desc* d, void* out, void* partial, const Co
   p.aw = reinterpret_cast<const unsigned char*>(d->b_w);
   p.bias = nullptr; p.res = nullptr; p.rmode = -1;
   p.out = out; p.stats = nullptr;
-  p.out_f32 = (d->out_dtype == CWDM_F32) ? 1 : 0;   // (the accurate fast mode's K-expanded skip, sg_shape_ok)
+  p.out_f32 = (d->out_dtype == CWDM_F32) ? 1 : 0;   // (the accurate fast mode's K-expanded skip)
   q.ntile16 = d->cout / 16;
   const SgGeom gm = sg_geom(d);
   q.parts = (int)gm.parts();
   q.tx = gm.tx; q.ty = gm.ty;
-  q.ksplit = sg_skip_ksplit(d, c.fp32x);
+  q.ksplit = ksplit;
   q.kper = ((d->b_c0 + d->b_c1) / 32 + q.ksplit - 1) / q.ksplit;
   q.part = reinterpret_cast<float*>(partial);
   CWDM_REQUIRE(q.ksplit == 1 || partial, CWDM_E_INVALID, "conv3d (small grid): K-split scratch missing");
   int rc;
   if ((rc = sg_counters(q, c.sync, q.ksplit > 1 ? reinterpret_cast<unsigned char*>(partial) +
-                                                      (int64_t)q.ksplit * d->B * ksplit_slice_voxels(d, c.fp32x) * d->cout * 4
+                                                      (int64_t)q.ksplit * d->B * q.parts * 256 * d->cout * 4
                                                 : nullptr, s)))
     return rc;
   return sg_go(q, d, 1, 2.0 * d->B * V * (double)d->cout * (d->b_c0 + d->b_c1), c.prof, s);

@@ -187,8 +187,6 @@ __global__ void __launch_bounds__(256) gn_fin_apply_kernel(GnFinApplyArgs a) {
   }
 }
 
-inline int64_t align256(int64_t n) { return (n + 255) & ~(int64_t)255; }
-
 int64_t src_voxels(const cwdm_conv3d_desc* d) {
   const int64_t V = d->D * d->H * d->W;
   return d->a_mode == 1 ? V / 8 : V;
@@ -196,84 +194,16 @@ int64_t src_voxels(const cwdm_conv3d_desc* d) {
 
 }  // namespace
 
-// kernel-path policy (cwdm_conv3d_set_path): 0 auto, 1 legacy only, 2 DMA kernels wherever the shape allows,
-// 3 as 2 without the warp-specialised kernel
-std::atomic<int> g_conv_path{env_int("CWDM_CONV_PATH", 0)};
-
 std::atomic<unsigned long long*> g_stamps{nullptr};
 
-int64_t v4_items(const cwdm_conv3d_desc* d) {
-  return d->B * ((d->W + 31) / 32) * (d->H / 4) * (d->D / 4) * (d->cout / 64);
-}
-
-// work items a launch aims for before it splits K (env CWDM_V4_KSPLIT_TARGET)
-int64_t v4_ksplit_target() {
-  // 64 (r04; was 128): config 5's 28^3 64-channel down-block convs (49 tiles)
-  // then run unsplit on 32-channel tiles: 44 -> 19 us against the split legacy path
-  static const int64_t t = env_ll("CWDM_V4_KSPLIT_TARGET", 64);
-  return t;
-}
-
-// K split of a grid with fewer tiles than two workgroups per CU (the 32^3
-// level): enough K slices for ~512 work items, at least two chunks per slice
-int v4_ksplit(const cwdm_conv3d_desc* d, const ConvCall& c) {
-  if (sg_eligible(d, c.fp32x)) return sg_ksplit(d, c.fp32x);  // the small-grid kernel's own K split (8^3 level)
-  const int ck = ck_of(d->dtype);
-  const int nch = (d->a_c0 + d->a_c1) / ck;
-  const int64_t nblk = v4_items(d);
-  const int64_t target = v4_ksplit_target();
-  if (nblk >= target || nch < 2) return 1;
-  // 16-bit: v4_launch doubles the work items with 32-channel tiles (no finishing
-  // passes) -- enough at config 5's 28^3 level (98 -> 196)
-  if (dtype_half(d->dtype) && 2 * nblk >= target && d->cout % 64 == 0) return 1;
-  int S = (int)std::min<int64_t>((target + nblk - 1) / nblk, nch / 2);
-  if (S < 1) S = 1;
-  const int per = (nch + S - 1) / S;
-  return (nch + per - 1) / per;
-}
-
-bool v4_eligible(const cwdm_conv3d_desc* d, const ConvCall& c) {
-  const int path = g_conv_path.load(std::memory_order_relaxed);
-  if (path == 1) return false;
-  // the 1x1 skip product is added through the residual slot: not both
-  if (d->b_w && d->res_mode >= 0) return false;
-  if (sg_eligible(d, c.fp32x)) return true;  // 16^3 / 8^3 levels: conv3d_sg.hip behind the same pre-passes
-  if (!dtype_compute(d->dtype)) return false;
-  // W >= kWideMinW: the statistics partials follow cwdm_conv3d_parts' 32-wide x tiles (pick_brick)
-  if (!d->a_w || d->W < kWideMinW || d->H % 4 || d->D % 4 || d->cout % 64) return false;
-  if (d->a_mode != 0 && d->a_mode != 1) return false;
-  if (d->res_mode < -1 || d->res_mode > 1) return false;
-  if (d->out1 && d->out_c0 % 8) return false;
-  const int64_t nblk = v4_items(d);
-  // work items: K slices, or (16-bit, no split, < 256 tiles) v4_launch's 32-channel tiles
-  const int S = v4_ksplit(d, c);
-  const int64_t items = nblk * S * (S == 1 && dtype_half(d->dtype) && nblk < 256 ? 2 : 1);
-  if (items < std::min<int64_t>(384, v4_ksplit_target()) && path < 2) return false;  // too few work items even K-split: the brick kernels
-  const int esz = dtype_size(d->dtype);
-  const int64_t sv = src_voxels(d);
-  // the DMA range check works on 32-bit byte offsets per batch
-  const int64_t lim = 0xFFFFE000LL;
-  if (d->a_gn) return sv * (d->a_c0 + d->a_c1) * esz < lim;
-  return sv * d->a_c0 * esz < lim && sv * d->a_c1 * esz < lim;
-}
-
-int64_t v4_workspace_bytes(const cwdm_conv3d_desc* d, const ConvCall& c) {
-  const int esz = dtype_size(d->dtype);
-  int64_t ws = 0;
-  if (d->a_gn) ws += align256(d->B * src_voxels(d) * (d->a_c0 + d->a_c1) * esz);
-  if (d->b_w) ws += align256(d->B * d->D * d->H * d->W * d->cout * esz);
-  // K-split slices of the conv, or of its 1x1 skip pre-pass (which runs first: one region serves both)
-  int S = v4_ksplit(d, c);
-  if (d->b_w) {
-    cwdm_conv3d_desc e = *d;
-    e.a_w = nullptr;
-    S = std::max(S, sg_skip_ksplit(&e, c.fp32x));
-  }
-  // (+ the small-grid kernel's K-split arrival counters behind the slices)
-  if (S > 1) ws += align256(S * d->B * ksplit_slice_voxels(d, c.fp32x) * d->cout * 4) + sg_sync_bytes(S);
-  // (+ a lone launch's apply-ahead sweep counters, last: conv3d_v4_forward)
-  if (d->a_gn) ws += kV5AaWords * 4;
-  return ws;
+int cu_count() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      return 256;
+    return n > 0 ? n : 256;
+  }();
+  return ncu;
 }
 
 int gnfin_flush(const cwdm_conv3d_desc* d, GnFinFuse* f, hipStream_t s) {
@@ -283,7 +213,6 @@ int gnfin_flush(const cwdm_conv3d_desc* d, GnFinFuse* f, hipStream_t s) {
                           f->eps, f->ss, f->mr, s);
 }
 
-namespace {
 // the fused finalize + pre-pass applies: 16-bit, every 16-channel chunk in one
 // source and whole groups, few partials per chunk (the small grids: <= 256 parts)
 bool gn_fin_fusable(const GnFinFuse& f, int dtype, int c0, int c1) {
@@ -298,6 +227,7 @@ bool gn_fin_fusable(const GnFinFuse& f, int dtype, int c0, int c1) {
   return cpg <= 16 && 16 % cpg == 0 && f.p0 <= 256 && (c1 == 0 || f.p1 <= 256) && f.voxels <= maxv;
 }
 
+namespace {
 int gn_fin_apply(const GnFinFuse& f, const void* x0, int c0, const void* x1, int c1, int64_t B, int64_t V, int dtype,
                  void* out, hipStream_t s) {
   GnFinApplyArgs a{};
@@ -322,23 +252,6 @@ int gn_fin_apply(const GnFinFuse& f, const void* x0, int c0, const void* x1, int
 }
 }  // namespace
 
-// the U-Net plan's backward: fuse the reduce pass of the SiLU(GroupNorm)
-// backward that follows this dgrad conv into its epilogue (GbwdFuse, conv3d_v4.hpp
-// V4Params::gx0); taken only by the 16-bit fast epilogue without K split (v4
-// only), and only where the conv leaves VALU room -- at 128^3 the
-// epilogue's ~13 VALU + 2 transcendentals per output element cost the
-// MFMA-bound kernel more (+30 %) than the separate reduce pass it saves; at
-// 32^3 it is a net win (same-box kernel traces).  At 64^3 it was too
-// against v4's plain dgrad (r03), but the warp-specialised kernel now takes those
-// dgrads faster than the fused v4 instance runs: 12 launches 3096 us fused vs 2547 +
-// 371 us of separate reduces (r06, profiles/r06/w_gbwd_maxw_ab.txt).  Env
-// CWDM_GBWD_MAXW, default 32.  Elsewhere the dgrad is an ordinary conv (v5 may take it).
-bool gbwd_grid_ok(const cwdm_conv3d_desc* d, const GbwdFuse* g) {
-  static const int gb_maxw = env_int("CWDM_GBWD_MAXW", 32);
-  return g && !g->used && dtype_half(d->dtype) && d->W <= gb_maxw && d->a_mode == 0 && d->res_mode < 0 &&
-         !d->stats;
-}
-
 int gn_apply(const void* x0, int c0, const void* x1, int c1, const float* gn, int64_t B, int64_t vpb, int dtype,
              void* out, hipStream_t s, int cm = 0) {
   constexpr int VPT = 4;
@@ -358,26 +271,25 @@ int gn_apply(const void* x0, int c0, const void* x1, int c1, const float* gn, in
   });
 }
 
-// launch of the DMA-staged kernel on prepared sources: a0 (c0 channels,
-// chunk-major if a0_cm) and a1 (c1 channels, channels-last), residual res/rmode;
-// partial: fp32 scratch of v4_ksplit(d, c) output slices (unused without a K split)
-int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
-              const void* res, int rmode, void* partial, ConvCall& c, hipStream_t s) {
+V4Params fill_params(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
+                     const void* res, int rmode, bool phase) {
   const int esz = dtype_size(d->dtype);
   const int ck = 32 / esz;
   const int64_t SV = src_voxels(d);
   V4Params p{};
   p.B = (int)d->B; p.D = (int)d->D; p.H = (int)d->H; p.W = (int)d->W;
+  // the phase instance tiles the source grid (the output is 2D x 2H x 2W)
+  if (phase) { p.D /= 2; p.H /= 2; p.W /= 2; }
   p.tx = (p.W + 31) / 32; p.ty = p.H / 4; p.tz = p.D / 4;
   p.cout = d->cout; p.nct = d->cout / 64;
   p.nch0 = c0 / ck; p.nch = (c0 + c1) / ck;
   p.a0 = a0; p.ac0 = c0; p.a1 = a1; p.ac1 = c1;
   p.a0_bstride = SV * c0 * esz; p.a1_bstride = SV * c1 * esz;
   p.a0_bytes = (unsigned)(SV * c0 * esz); p.a1_bytes = (unsigned)(SV * c1 * esz);
-  p.amode = d->a_mode;
+  p.amode = phase ? 0 : d->a_mode;
   p.a0_cm = a0_cm;
   p.a0_cvox = (int)SV;
-  p.aw = reinterpret_cast<const unsigned char*>(d->a_w);
+  p.aw = reinterpret_cast<const unsigned char*>(phase ? d->a_w_phase : d->a_w);
   p.bias = d->bias; p.bias_bs = d->bias_bstride;
   p.res = res; p.rmode = rmode;
   p.out = d->out;
@@ -386,14 +298,29 @@ int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
   p.out1 = d->out1; p.out_c0 = d->out_c0;
   p.accumulate = d->accumulate;
   p.stamps = g_stamps.load(std::memory_order_relaxed);
-  if (sg_eligible(d, c.fp32x)) return sg_launch(p, d, partial, c, s);
-  // the warp-specialised kernel (conv3d_v5.hip) where it applies (not the
-  // backward's fused GroupNorm-reduce dgrad, not the stamps diagnostics build)
-  // an upsampling conv as eight phase convs on the source grid, where its phase weights came along
-  if (v5_phase_ok(d, rmode, c)) return v5_launch(d, a0, c0, a1, c1, a0_cm, nullptr, nullptr, -1, c, s, nullptr, true);
-  if (v5_eligible(d, false, c))   // (refuses the dgrad that takes the fused GroupNorm-backward reduce)
-    return v5_launch(d, a0, c0, a1, c1, a0_cm, nullptr, res, rmode, c, s);
-  const int S = v4_ksplit(d, c);
+  return p;
+}
+
+// launch of the route's kernel on prepared sources: a0 (c0 channels, chunk-major if a0_cm) and a1
+// (c1 channels, channels-last), residual res / rmode; r: conv_route's, or conv_route_prepared(d, rmode, c);
+// partial: fp32 scratch of r.ksplit output slices (unused without a K split)
+int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
+              const void* res, int rmode, void* partial, const ConvRoute& r, ConvCall& c, hipStream_t s) {
+  switch (r.kernel) {
+    case ConvKernel::SmallGrid:
+      return sg_launch(fill_params(d, a0, c0, a1, c1, a0_cm, res, rmode), d, r.ksplit, partial, c, s);
+    case ConvKernel::V5Phase:
+      return v5_launch(d, a0, c0, a1, c1, a0_cm, nullptr, nullptr, -1, c, s, nullptr, true);
+    case ConvKernel::V5:
+    case ConvKernel::V5Split:
+      return v5_launch(d, a0, c0, a1, c1, a0_cm, nullptr, res, rmode, c, s);
+    case ConvKernel::V4:
+      break;
+    default:
+      return fail(CWDM_E_INVALID, "conv3d: not a route of the DMA-staged launchers");
+  }
+  V4Params p = fill_params(d, a0, c0, a1, c1, a0_cm, res, rmode);
+  const int S = r.ksplit;
   p.ksplit = S;
   p.kper = (p.nch + S - 1) / S;
   if (S > 1) {
@@ -402,22 +329,12 @@ int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
     p.bias = nullptr; p.res = nullptr; p.rmode = -1; p.stats = nullptr;
     p.out = partial; p.out_f32 = 1; p.out1 = nullptr; p.out_c0 = 0; p.accumulate = 0;
   }
-  // fewer 64-channel tiles than CUs (the 32^3 level): 32-channel tiles, one
-  // z-plane per wave (twice the work items; the statistics bricks are the same)
-  static const bool ct32_on = env_not0("CWDM_V4_CT32");
-  const bool ct32 = ct32_on && dtype_half(d->dtype) && S == 1 && !p.out_f32 && !p.accumulate && !p.out1 &&
-                    (long long)p.B * p.tx * p.ty * p.tz * p.nct < 256 &&
-                    (long long)p.D * p.H * p.W * p.cout * 2 < 0xFFFFE000LL;
+  const bool ct32 = r.ct32, fast = r.fast;
   if (ct32) p.nct = d->cout / 32;
   const long long nblk = (long long)p.B * p.tx * p.ty * p.tz * p.nct * S;
   p.nblk = (int)nblk;
   // persistent: two workgroups per CU (80 KB LDS, <= 256 registers per lane each)
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return 256;
-    return n > 0 ? n : 256;
-  }();
+  const int ncu = cu_count();
   // workgroups per CU slot of the persistent grid (env CWDM_V4_GRID_MULT, A/B knob)
   static const long long gmul = env_ll("CWDM_V4_GRID_MULT", 4);
   const dim3 grid((unsigned)std::min<long long>(nblk, gmul * ncu));
@@ -426,9 +343,6 @@ int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
   // bench.py A/B on one MI355X): no delay 57.15 vs half-tile 56.80 steps/s
   static const int stagger_env = env_int("CWDM_CONV_STAGGER", 0);
   p.stagger_cycles = nblk > 2LL * ncu ? (stagger_env >= 0 ? stagger_env : (p.nch * 17000 + 12000) / 2) : 0;
-  // the fast epilogue addresses output / residual through 32-bit buffer offsets per batch
-  const bool fast = !p.out_f32 && !p.accumulate && !p.out1 &&
-                    (long long)p.D * p.H * p.W * p.cout * 2 < 0xFFFFE000LL;
   prof_begin(c.prof, s);
   auto launch16 = [&](auto tag) {
     using T = decltype(tag);
@@ -446,21 +360,14 @@ int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
       else hipLaunchKernelGGL((conv3d_v4_kernel<T, 0, false>), grid, dim3(256), 0, s, p);
     }
   };
-  // (gbwd_grid_ok: where the fused reduce pays)
-  if (gbwd_grid_ok(d, c.gbwd) && (ct32 || fast) && S == 1 && rmode < 0 && !p.stats && p.amode == 0) {
+  if (r.takes_gbwd) {   // the fused GroupNorm-backward reduce
     GbwdFuse& g = *c.gbwd;
-    const int nc = ct32 ? 32 : 64;
-    const int C = d->cout;
-    const long long need = (long long)p.B * p.tx * p.ty * p.tz * C * 8;
-    if (g.groups > 0 && C % g.groups == 0 && C / g.groups >= 2 && g.c0 % nc == 0 && g.c0 <= C &&
-        (g.c0 == C || g.x1) && need <= g.part_bytes) {
-      p.gx0 = g.x0; p.gx1 = g.x1; p.gc0 = g.c0;
-      p.gss = g.ss; p.gmr = g.mr; p.ggroups = g.groups;
-      p.gdiv = make_fastdiv((unsigned)(C / g.groups));
-      p.stats = g.part;
-      g.used = true;
-      g.nblk = p.tx * p.ty * p.tz;
-    }
+    p.gx0 = g.x0; p.gx1 = g.x1; p.gc0 = g.c0;
+    p.gss = g.ss; p.gmr = g.mr; p.ggroups = g.groups;
+    p.gdiv = make_fastdiv((unsigned)(d->cout / g.groups));
+    p.stats = g.part;
+    g.used = true;
+    g.nblk = p.tx * p.ty * p.tz;
   }
   if (d->dtype == CWDM_BF16) {
     launch16(bf16_t{});
@@ -490,7 +397,7 @@ int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
     q.accumulate = d->accumulate;
     q.ksplit = 1;
     q.partial = part;
-    const dim3 rg((unsigned)v4_items(d));
+    const dim3 rg((unsigned)((long long)p.B * p.tx * p.ty * p.tz * (p.cout / 64)));
     dispatch_dtype(d->dtype, [&](auto tag) -> int {
       using T = decltype(tag);
       hipLaunchKernelGGL((conv3d_reduce_kernel<T, 32, 4, 4, 2>), rg, dim3(256), 0, s, q, 1);
@@ -501,30 +408,17 @@ int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
   return CWDM_OK;
 }
 
-int conv3d_v4_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s) {
-  const int esz = dtype_size(d->dtype);
+// a conv of the DMA path by its route: the GroupNorm'd input, the 1x1 skip product, the launch.  The
+// workspace (>= r.ws_total: conv3d_forward) is carved in ConvRoute's region order
+int conv3d_v4_forward(const cwdm_conv3d_desc* d, const ConvRoute& r, ConvCall& c, hipStream_t s) {
   unsigned char* ws = reinterpret_cast<unsigned char*>(d->workspace);
-  const int64_t SV = src_voxels(d);
   const void* a0 = d->a0;
   const void* a1 = d->a1;
   int c0 = d->a_c0, c1 = d->a_c1;
   int a0_cm = 0;
   int rc;
-  // GroupNorm + SiLU inside the warp-specialised conv (no activated copy):
-  // inference only -- the training forward keeps the activated input for wgrad
-  const float* agn = nullptr;
-  if (d->a_gn && !c.act_keep && v5_eligible(d, true, c)) agn = d->a_gn;
-  // or the warp-specialised conv writes the activated copy itself, ahead of its sweep (apply-ahead:
-  // no pre-pass over HBM; the training forward keeps the copy it writes)
   V5Aa aa{};
-  aa.units = (d->a_gn && !agn) ? v5_aa_units(d, c, &aa.lead) : 0;
-  // an offered GroupNorm finalize (GnFinFuse): fused into the pre-pass below where it fits, else run now
-  GnFinFuse* fin = (c.gnfin && !c.gnfin->used && d->a_gn && c.gnfin->ss == d->a_gn) ? c.gnfin : nullptr;
-  if (fin && (agn || aa.units || !gn_fin_fusable(*fin, d->dtype, c0, c1))) {
-    if ((rc = gnfin_flush(d, fin, s))) return rc;
-    fin = nullptr;
-  }
-  if (d->a_gn && !agn) {
+  if (d->a_gn && !r.gn_in_lds()) {
     // the activated input: in the workspace, or (training) where the plan keeps
     // it for the backward's DMA-staged wgrad
     void* act = ws;
@@ -532,22 +426,21 @@ int conv3d_v4_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s) {
       act = c.act_keep;
       c.act_kept = true;
     } else {
-      ws += align256(d->B * SV * (c0 + c1) * esz);
+      ws += r.ws_act;
     }
-    if (aa.units) {
+    if (r.kernel == ConvKernel::V5Aa) {
+      aa.units = r.aa_units; aa.lead = r.aa_lead;
       aa.x0 = a0; aa.c0 = c0; aa.x1 = a1; aa.c1 = c1; aa.gn = d->a_gn;
       // the sweep counters: the plan's zeroed sync block, else this launch's workspace tail (zeroed here)
       aa.cnt = plan_aa_counters(c.sync);
       if (!aa.cnt) {
-        const int64_t need = v4_workspace_bytes(d, c);
-        CWDM_REQUIRE(d->workspace && d->ws_bytes >= need, CWDM_E_WORKSPACE, "conv3d (apply-ahead): workspace too small");
-        aa.cnt = reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(d->workspace) + need - kV5AaWords * 4);
-        CWDM_HIP(hipMemsetAsync(aa.cnt, 0, kV5AaWords * 4, s));
+        aa.cnt = reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(d->workspace) + r.ws_total - r.ws_aa);
+        CWDM_HIP(hipMemsetAsync(aa.cnt, 0, r.ws_aa, s));
       }
-    } else if (fin) {
-      fin->used = true;
-      if ((rc = gn_fin_apply(*fin, a0, c0, a1, c1, d->B, SV, d->dtype, act, s))) return rc;
-    } else if ((rc = gn_apply(a0, c0, a1, c1, d->a_gn, d->B, SV, d->dtype, act, s, 1))) {
+    } else if (r.gn == GnInput::FinApply) {
+      c.gnfin->used = true;
+      if ((rc = gn_fin_apply(*c.gnfin, a0, c0, a1, c1, d->B, src_voxels(d), d->dtype, act, s))) return rc;
+    } else if ((rc = gn_apply(a0, c0, a1, c1, d->a_gn, d->B, src_voxels(d), d->dtype, act, s, 1))) {
       return rc;
     }
     a0 = act; c0 = c0 + c1; a1 = nullptr; c1 = 0;
@@ -557,26 +450,22 @@ int conv3d_v4_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s) {
   int rmode = d->res_mode;
   if (d->b_w) {
     void* skip = ws;
-    ws += align256(d->B * d->D * d->H * d->W * d->cout * esz);
-    cwdm_conv3d_desc e = *d;
-    e.a0 = nullptr; e.a1 = nullptr; e.a_c0 = 0; e.a_c1 = 0; e.a_gn = nullptr; e.a_w = nullptr; e.a_mode = 0;
-    e.bias = nullptr; e.bias_bstride = 0; e.stats = nullptr;
-    e.out = skip; e.out_dtype = d->dtype; e.out1 = nullptr; e.out_c0 = 0; e.accumulate = 0;
-    e.workspace = nullptr; e.ws_bytes = 0;
-    if (sg_skip_eligible(&e, c.fp32x)) {
-      if ((rc = sg_skip_launch(&e, skip, ws, c, s))) return rc;   // ws: the K-split region, free until the conv
-    } else if (pw_eligible(&e)) {
-      if ((rc = pw_forward(&e, c, s))) return rc;
-    } else if (pw_split_eligible(&e)) {
-      if ((rc = pw_split_forward(&e, c.prof, s))) return rc;
-    } else if ((rc = legacy_conv3d_forward(&e, c.prof, s))) {
-      return rc;
+    ws += r.ws_skip;
+    const cwdm_conv3d_desc e = skip_desc(d, skip);
+    switch (r.skip) {
+      case SkipKernel::SmallGrid:   // ws: the K-split region, free until the conv
+        rc = sg_skip_launch(&e, skip, ws, r.skip_ksplit, c, s);
+        break;
+      case SkipKernel::Pw: rc = pw_forward(&e, c, false, s); break;
+      case SkipKernel::PwSplit: rc = pw_split_forward(&e, c.prof, s); break;
+      default: rc = legacy_conv3d_forward(&e, c.prof, s);
     }
+    if (rc) return rc;
     res = skip; rmode = 0;
   }
-  if (agn) return v5_launch(d, a0, c0, a1, c1, 0, agn, res, rmode, c, s);
-  if (aa.units) return v5_launch(d, a0, c0, nullptr, 0, 1, nullptr, res, rmode, c, s, &aa);
-  return v4_launch(d, a0, c0, a1, c1, a0_cm, res, rmode, v4_ksplit(d, c) > 1 ? ws : nullptr, c, s);
+  if (r.gn_in_lds()) return v5_launch(d, a0, c0, a1, c1, 0, d->a_gn, res, rmode, c, s);
+  if (r.kernel == ConvKernel::V5Aa) return v5_launch(d, a0, c0, nullptr, 0, 1, nullptr, res, rmode, c, s, &aa);
+  return v4_launch(d, a0, c0, a1, c1, a0_cm, res, rmode, r.ksplit > 1 ? ws : nullptr, r, c, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -755,11 +644,6 @@ extern "C" int cwdm_gn_apply(const void* x0, int c0, const void* x1, int c1, con
                "cwdm_gn_apply: channels must be multiples of 8");
   CWDM_REQUIRE(dtype_compute(dtype), CWDM_E_INVALID, "cwdm_gn_apply: bad dtype");
   return gn_apply(x0, c0, x1, c1, gn, B, voxels, dtype, out, (hipStream_t)stream);
-}
-
-extern "C" int cwdm_conv3d_set_path(int path) {
-  CWDM_REQUIRE(path >= 0 && path <= 3, CWDM_E_INVALID, "cwdm_conv3d_set_path: path must be 0, 1, 2 or 3");
-  return g_conv_path.exchange(path);
 }
 
 // diagnostics: the DMA-staged conv kernel writes 24 u64 per workgroup (s_memtime

@@ -104,11 +104,14 @@ __device__ unsigned g_v4_cu_arrivals[8 * 256];
 
 // conv3d_v5 apply-ahead arguments (conv3d_v5.hip): the raw sources of a GroupNorm'd input, their
 // scale / shift, the sweep lead and the per-chunk share of the kernel instance (v5_aa_units)
-constexpr int kV5AaWords = 4096;   // apply-ahead sweep counters of one launch (conv3d_v5.hip kV5AaCnt)
 struct V5Aa { const void* x0; int c0; const void* x1; int c1; const float* gn; int lead, units; unsigned* cnt; };
 
 // the launchers that take these (the rest of the cross-unit interface: internal.hpp)
-int sg_launch(const V4Params& v, const cwdm_conv3d_desc* d, void* partial, const ConvCall& c,
+// what of V4Params follows from the desc and the prepared sources (a0: c0 channels, chunk-major if a0_cm;
+// a1: c1 channels, channels-last; the residual res / rmode); phase: the phase instance's source-grid tiling
+V4Params fill_params(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
+                     const void* res, int rmode, bool phase = false);   // conv3d_v4.hip
+int sg_launch(const V4Params& v, const cwdm_conv3d_desc* d, int ksplit, void* partial, const ConvCall& c,
               hipStream_t s);   // conv3d_sg.hip
 int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
               const float* agn, const void* res, int rmode, ConvCall& c, hipStream_t s, const V5Aa* aa = nullptr,

@@ -1303,13 +1303,6 @@ __global__ void __launch_bounds__(512) conv3d_v5s_kernel(V4Params p) {
   }
 }
 
-namespace {
-int v5_mode() {
-  static const int m = env_int("CWDM_V5", 3);
-  return m;
-}
-}  // namespace
-
 std::atomic<int> g_v5_grid{0};
 std::atomic<int> g_v5_aa{env_int("CWDM_V5_AA", 1)};
 std::atomic<int> g_v5_aa_launches{0};
@@ -1320,15 +1313,6 @@ std::atomic<int> g_v5_aa_extra{0};
 std::atomic<int> g_v5_aa_spin{0};
 
 namespace {
-int v5_ncu() {
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return 256;
-    return n > 0 ? n : 256;
-  }();
-  return ncu;
-}
 // the persistent grid of an apply-ahead launch: every workgroup must be resident at once (its counter
 // waits span the grid), so never more than the CUs x the instance's occupancy, whatever the debug cap
 int v5_aa_grid(int64_t nblk) {
@@ -1339,67 +1323,16 @@ int v5_aa_grid(int64_t nblk) {
     return n > 0 ? n : 1;
   }();
   const int cap = g_v5_grid.load(std::memory_order_relaxed);
-  const int64_t lim = (int64_t)v5_ncu() * occ;
-  return (int)std::min<int64_t>(nblk, cap > 0 ? std::min<int64_t>(cap, lim) : v5_ncu());
+  const int64_t lim = (int64_t)cu_count() * occ;
+  return (int)std::min<int64_t>(nblk, cap > 0 ? std::min<int64_t>(cap, lim) : cu_count());
 }
 }  // namespace
-
-// the warp-specialised kernel takes a conv of the DMA path when it is a 16-bit
-// fast-epilogue conv without K split and with at least one tile per CU (CWDM_V5_MIN_TPC)
-// (env CWDM_V5: 0 off, 1 GroupNorm'd inputs only, 2 every eligible conv, 3 (default)
-// every eligible conv with the GroupNorm applied by the cwdm_gn_apply pre-pass: the
-// in-LDS transform costs the helper waves more issue cycles than the MFMA waves
-// leave them -- measured 611 vs 588 us on the 64->64 128^3-subband conv)
-bool v5_eligible(const cwdm_conv3d_desc* d, bool gn, const ConvCall& c) {
-  const int mode = v5_mode();
-  const int path = g_conv_path.load(std::memory_order_relaxed);
-  if (d->dtype == CWDM_F32) {
-    // the accurate fast mode (conv3d_v5s_kernel): wherever the split weights are
-    // given and the shape tiles (no minimum work: it is 8x the exact-fp32 MFMA rate)
-    if (!d->a_w_split || path == 1 || path == 3) return false;
-    if (d->out_dtype != CWDM_F32 || d->accumulate || d->out1) return false;
-    if (d->a_mode != 0 && d->a_mode != 1) return false;
-    if (d->a_c0 % 16 || d->a_c1 % 16) return false;   // pairs of 8-channel fp32 chunks, never straddling the sources
-    if (d->res_mode < -1 || d->res_mode > 1) return false;
-    // the 1x1 skip product is added through the residual slot (conv3d_v4_forward): not both
-    if (d->b_w && d->res_mode >= 0) return false;
-    if (d->W < kWideMinW || d->H % 4 || d->D % 4 || d->cout % 64) return false;
-    // 32-bit buffer offsets per batch: the output, and the sources (raw, or the
-    // activated (c0 + c1)-channel copy of the training forward's pre-pass)
-    const int64_t lim = 0xFFFFE000LL;
-    if (d->D * d->H * d->W * d->cout * 4 >= lim) return false;
-    const int64_t sv = d->a_mode == 1 ? d->D * d->H * d->W / 8 : d->D * d->H * d->W;
-    if (d->a_gn ? sv * (d->a_c0 + d->a_c1) * 4 >= lim : (sv * d->a_c0 * 4 >= lim || sv * d->a_c1 * 4 >= lim))
-      return false;
-    return !(gn && d->a_mode == 1);
-  }
-  if (mode <= 0 || (mode == 1 && !gn) || path == 1 || path == 3) return false;
-  // GroupNorm+SiLU in LDS: not for an upsampling conv (its halo repeats every
-  // source voxel 8x: the pre-pass at the half resolution is 8x cheaper), and
-  // not in mode 3 (pre-pass + this kernel on the activated copy)
-  if (gn && (d->a_mode == 1 || mode == 3)) return false;
-  if (!dtype_half(d->dtype) || sg_eligible(d, c.fp32x)) return false;
-  if (path != 2 && v4_ksplit(d, c) != 1) return false;   // (path 2: forced, no K split of its own)
-  if (d->out_dtype != d->dtype || d->accumulate || d->out1) return false;
-  if (d->a_mode != 0 && d->a_mode != 1) return false;
-  if (d->res_mode < -1 || d->res_mode > 1) return false;
-  if (d->W < kWideMinW || d->H % 4 || d->D % 4 || d->cout % 64) return false;
-  if (d->D * d->H * d->W * d->cout * 2 >= 0xFFFFE000LL) return false;
-  if (d->a_c0 + d->a_c1 < 32) return false;   // >= 2 chunks per tile: a tile's drain spans two chunks
-  if (gbwd_grid_ok(d, c.gbwd)) return false;   // the backward's fused dgrad instance is v4's
-  const int ncu = v5_ncu();
-  // tiles per CU below which v4 (two workgroups per CU) keeps the conv (env
-  // CWDM_V5_MIN_TPC, A/B knob; 1 since r04: config 5's 56^3 64-channel convs,
-  // 392 tiles, 57 -> 53 us on v5)
-  static const double min_tpc = env_double("CWDM_V5_MIN_TPC", 1.0);
-  return path == 2 || (double)v4_items(d) >= min_tpc * ncu;
-}
 
 // the persistent grid of a plain launch: one workgroup per CU (or the debug cap), never more than the items
 namespace {
 unsigned v5_grid(long long nblk) {
   const int cap = g_v5_grid.load(std::memory_order_relaxed);
-  return (unsigned)std::min<long long>(nblk, cap > 0 ? cap : v5_ncu());
+  return (unsigned)std::min<long long>(nblk, cap > 0 ? cap : cu_count());
 }
 }  // namespace
 
@@ -1409,16 +1342,15 @@ unsigned v5_grid(long long nblk) {
 // workgroup wherever the caller asks for them (ConvCall::stats_wg) and the rows fit; per tile one row per (source tile,
 // phase), laid out as the 2 tx x 2 ty x 2 tz output bricks -- only where those are the rows the caller
 // holds (cwdm_conv3d_parts of the output grid: ceil(W / 32) == 2 ceil(W / 64)), else the gather path.
-bool v5_phase_ok(const cwdm_conv3d_desc* d, int rmode, const ConvCall& c) {
+bool v5_phase_ok(const cwdm_conv3d_desc* d, int rmode, bool stats_wg) {
   if (!d->a_w_phase || !g_up_phase.load(std::memory_order_relaxed)) return false;
   if (!dtype_half(d->dtype) || d->a_mode != 1 || d->b_w || rmode != -1 || d->res_mode != -1) return false;
-  if (!v5_eligible(d, false, c)) return false;
   const int64_t SD = d->D / 2, SH = d->H / 2, SW = d->W / 2;
   if (SW < kWideMinW || SH % 4 || SD % 4) return false;
   if (d->stats) {
     const int64_t stx = (SW + 31) / 32, otx = (d->W + 31) / 32, otiles = otx * (d->H / 4) * (d->D / 4);
     const long long nblk = (long long)d->B * stx * (SH / 4) * (SD / 4) * (d->cout / 64) * 8;
-    const bool wg = c.stats_wg && d->B == 1 && d->cout / 64 <= 2 && (long long)v5_grid(nblk) <= otiles;
+    const bool wg = stats_wg && d->B == 1 && d->cout / 64 <= 2 && (long long)v5_grid(nblk) <= otiles;
     if (!wg && otx != 2 * stx) return false;
   }
   return true;
@@ -1428,12 +1360,11 @@ bool v5_phase_ok(const cwdm_conv3d_desc* d, int rmode, const ConvCall& c) {
 // agn: [B][c0 + c1][2] GroupNorm scale / shift applied in LDS (null: none)
 // apply-ahead (conv3d_v5_kernel<.., AA>) for a GroupNorm'd conv input: the per-chunk share AA (1, 2, 4,
 // 8 steps of 256 lanes) its sweep needs, or 0 where it does not apply (env CWDM_V5_AA=0: never)
-int v5_aa_units(const cwdm_conv3d_desc* d, const ConvCall& c, int* lead) {
+int v5_aa_units(const cwdm_conv3d_desc* d, int* lead) {
   const int mode = g_v5_aa.load(std::memory_order_relaxed);
   if (!mode || !d->a_gn || d->B != 1 || d->a_mode != 0 || !dtype_half(d->dtype)) return 0;
   const int C = d->a_c0 + d->a_c1;
   if (d->a_c0 % 8 || d->a_c1 % 8 || C % 16 || C > 2048) return 0;
-  if (!v5_eligible(d, false, c)) return 0;
   // the helpers' share per chunk fits beside the drain from 8 input chunks (r05 stamps: the
   // 4-chunk 64-channel convs left them ~4k cycles behind the MFMA waves per chunk); env
   // CWDM_V5_AA_MINCH (A/B knob)
@@ -1469,30 +1400,10 @@ int v5_aa_units(const cwdm_conv3d_desc* d, const ConvCall& c, int* lead) {
 
 int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
               const float* agn, const void* res, int rmode, ConvCall& c, hipStream_t s, const V5Aa* aa, bool phase) {
-  const int esz = dtype_size(d->dtype);
-  const int ck = 32 / esz;
-  const int64_t SV = d->a_mode == 1 ? d->D * d->H * d->W / 8 : d->D * d->H * d->W;
   CWDM_REQUIRE(!agn || !a0_cm, CWDM_E_INVALID, "conv3d_v5: GroupNorm applies to raw channels-last sources only");
   CWDM_REQUIRE(!phase || (d->a_w_phase && d->a_mode == 1 && !agn && !aa && rmode < 0 && dtype_half(d->dtype)),
                CWDM_E_INVALID, "conv3d_v5: phase arguments");
-  V4Params p{};
-  p.B = (int)d->B; p.D = (int)d->D; p.H = (int)d->H; p.W = (int)d->W;
-  // the phase instance tiles the source grid (the output is 2D x 2H x 2W)
-  if (phase) { p.D /= 2; p.H /= 2; p.W /= 2; }
-  p.tx = (p.W + 31) / 32; p.ty = p.H / 4; p.tz = p.D / 4;
-  p.cout = d->cout; p.nct = d->cout / 64;
-  p.nch0 = c0 / ck; p.nch = (c0 + c1) / ck;
-  p.a0 = a0; p.ac0 = c0; p.a1 = a1; p.ac1 = c1;
-  p.a0_bstride = SV * c0 * esz; p.a1_bstride = SV * c1 * esz;
-  p.a0_bytes = (unsigned)(SV * c0 * esz); p.a1_bytes = (unsigned)(SV * c1 * esz);
-  p.amode = phase ? 0 : d->a_mode;
-  p.a0_cm = a0_cm;
-  p.a0_cvox = (int)SV;
-  p.aw = reinterpret_cast<const unsigned char*>(phase ? d->a_w_phase : d->a_w);
-  p.bias = d->bias; p.bias_bs = d->bias_bstride;
-  p.res = res; p.rmode = rmode;
-  p.out = d->out;
-  p.stats = d->stats;
+  V4Params p = fill_params(d, a0, c0, a1, c1, a0_cm, res, rmode, phase);
   p.ksplit = 1; p.kper = p.nch;
   p.agn = agn;
   if (aa) {
@@ -1513,7 +1424,6 @@ int v5_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1,
   static const int diag = env_int("CWDM_V5_DIAGMASK", 0);
   p.diag = diag;
 #endif
-  p.stamps = g_stamps.load(std::memory_order_relaxed);
   const long long nblk = (long long)p.B * p.tx * p.ty * p.tz * p.nct * (phase ? 8 : 1);
   CWDM_REQUIRE(nblk < (1LL << 31), CWDM_E_UNSUPPORTED, "conv3d_v5: too many work items");
   p.nblk = (int)nblk;

@@ -13,7 +13,7 @@
 namespace cwdm {
 
 // ---- conv routing (cwdm_conv3d_forward, conv3d.hip) -----------------------
-// kernel-path policy (cwdm_conv3d_set_path; conv3d_v4.hip) and the diagnostics
+// kernel-path policy (cwdm_conv3d_set_path; conv_route.cpp) and the diagnostics
 // builds' stamp buffer (cwdm_debug_conv_stamps)
 extern std::atomic<int> g_conv_path;
 extern std::atomic<unsigned long long*> g_stamps;
@@ -40,6 +40,61 @@ struct ConvCall {
 // cwdm_conv3d_forward with its context
 int conv3d_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s);
 
+// ---- the route of one conv call (conv_route.cpp) --------------------------
+// Everything that is decided about a conv before anything is launched: which
+// kernel runs it, how its GroupNorm'd input and its 1x1 skip product are
+// prepared, its K split, what it takes of the context's offers, and its
+// workspace.  conv_route is the one place that decides; the launch path
+// (conv3d.hip, conv3d_v4.hip), cwdm_conv3d_workspace_bytes and the U-Net
+// plan's layout read the result.
+enum class ConvKernel {
+  Head,        // conv3d_head.hip: the output head
+  Pointwise,   // pointwise.hip: a pure 1x1
+  SmallGrid,   // conv3d_sg.hip (W < kWideMinW)
+  V5Phase,     // conv3d_v5.hip, an upsampling conv as eight phase convs
+  V5,          // conv3d_v5.hip on raw or pre-activated sources
+  V5Gn,        //   ... applying the GroupNorm in LDS
+  V5Aa,        //   ... writing the activated copy ahead of its own sweep (aa_units, aa_lead)
+  V5Split,     // conv3d_v5s_kernel: fp32 through split-bf16 weights (a_w_split)
+  V4,          // conv3d_v4.hpp
+  Brick        // conv3d_kernels.hpp: every shape and mode
+};
+enum class GnInput { None, Apply, FinApply, InKernel };   // the gn_apply / gn_fin_apply pre-pass, or the kernel's own
+enum class SkipKernel { None, SmallGrid, Pw, PwSplit, Brick };   // d->b_w beside a 3x3x3 conv: runs first, added as the residual
+struct ConvRoute {
+  ConvKernel kernel = ConvKernel::Brick;
+  GnInput gn = GnInput::None;
+  SkipKernel skip = SkipKernel::None;
+  int ksplit = 1, skip_ksplit = 1;
+  int aa_units = 0, aa_lead = 0;
+  bool flush_fin = false;      // an offered GroupNorm finalize (ConvCall::gnfin) runs first, on its own
+  bool v4_ok = false;          // the v4 kernel's shape / work rule holds (the fused GroupNorm + skip pass of the plan asks)
+  bool ct32 = false, fast = false;   // V4: 32-channel tiles / the 32-bit-offset epilogue
+  // what the call takes of its context
+  bool takes_gbwd = false, takes_gapply = false, keeps_act = false;
+  // workspace regions, in this order: the activated input | the skip product | the K-split slices with their
+  // counters | the apply-ahead counters.  Sizes, conservatively: a region is counted where the desc could
+  // use it (ws_act for any a_gn, ws_aa likewise), so the total depends on the desc's shape alone.
+  int64_t ws_act = 0, ws_skip = 0, ws_ksplit = 0, ws_aa = 0, ws_total = 0;
+  bool on_dma() const { return kernel != ConvKernel::Head && kernel != ConvKernel::Pointwise && kernel != ConvKernel::Brick; }
+  bool gn_in_lds() const { return gn == GnInput::InKernel && kernel != ConvKernel::V5Aa; }
+};
+// the preferred route of (d, c), whatever workspace d brings (conv3d_forward demotes to Brick below ws_total)
+ConvRoute conv_route(const cwdm_conv3d_desc* d, const ConvCall& c);
+// the route of a launch on prepared sources (v4_launch): GroupNorm applied, the skip product, if any,
+// in the residual slot (rmode: the residual mode the launch sees) -- the kernel and its K split only
+ConvRoute conv_route_prepared(const cwdm_conv3d_desc* d, int rmode, const ConvCall& c);
+// cwdm_conv3d_workspace_bytes with the route in hand: the route's regions, or the brick kernels' split-K slices
+int64_t conv_workspace_bytes(const cwdm_conv3d_desc* d, const ConvRoute& r);
+// the kernel (skip) and K split (skip_ksplit) of a 1x1 skip product e run on its own, as conv_route
+// picks them for the skip beside a 3x3x3 conv
+ConvRoute conv_route_skip(const cwdm_conv3d_desc* e, const ConvCall& c);
+// the 1x1 skip product of d on its own (segment B only, the output written in the compute dtype)
+cwdm_conv3d_desc skip_desc(const cwdm_conv3d_desc* d, void* out);
+// compute units of the device (256 without one)
+int cu_count();
+constexpr int kV5AaWords = 4096;   // apply-ahead sweep counters of one launch (conv3d_v5.hip kV5AaCnt)
+
 // conv3d.hip: the brick / split-K kernels, and the weight packs as jobs (the public packs'
 // checks and error codes; a caller batches its jobs through pack_batch_run)
 int legacy_conv3d_forward(const cwdm_conv3d_desc* d, ProfHook* prof, hipStream_t s);
@@ -59,42 +114,32 @@ int head_split3_pack(const float* w, int cout, int cin, float* tmp, void* out, h
 int split3_prep(const float* x0, int c0, const float* x1, int c1, const float* gn, int64_t B, int64_t V, int cm,
                 void* x3, hipStream_t s);
 
-// pointwise.hip: 1x1 convs (pw_gapply_ok: the skip dgrad can take a GapplyFuse)
-bool pw_eligible(const cwdm_conv3d_desc* d);
-int pw_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s);
-bool pw_gapply_ok(const cwdm_conv3d_desc* d);
-bool pw_split_eligible(const cwdm_conv3d_desc* d);
+// pointwise.hip: 1x1 convs (gapply: the launch takes c.gapply, ConvRoute::takes_gapply)
+int pw_forward(const cwdm_conv3d_desc* d, ConvCall& c, bool gapply, hipStream_t s);
 int pw_split_forward(const cwdm_conv3d_desc* d, ProfHook* prof, hipStream_t s);
 
-// conv3d_v4.hip: the DMA-staged conv and its pre-passes
-bool v4_eligible(const cwdm_conv3d_desc* d, const ConvCall& c);
-int64_t v4_items(const cwdm_conv3d_desc* d);
-int v4_ksplit(const cwdm_conv3d_desc* d, const ConvCall& c);
-int64_t v4_workspace_bytes(const cwdm_conv3d_desc* d, const ConvCall& c);
-int conv3d_v4_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s);
+// conv3d_v4.hip: the DMA-staged conv and its pre-passes, by the route r
+int conv3d_v4_forward(const cwdm_conv3d_desc* d, const ConvRoute& r, ConvCall& c, hipStream_t s);
 int v4_launch(const cwdm_conv3d_desc* d, const void* a0, int c0, const void* a1, int c1, int a0_cm,
-              const void* res, int rmode, void* partial, ConvCall& c, hipStream_t s);
-bool gbwd_grid_ok(const cwdm_conv3d_desc* d, const GbwdFuse* g);
+              const void* res, int rmode, void* partial, const ConvRoute& r, ConvCall& c, hipStream_t s);
 bool apply_skip_ok(int dtype, int C, int cout, int64_t B, int64_t vpb);
 int gn_apply_skip(const void* x0, int c0, const void* x1, int c1, const float* gn, int64_t B, int64_t vpb, int dtype,
                   const void* wskip, int cout, void* act, void* skip, hipStream_t s);
+// the fused finalize + pre-pass takes the offered finalize f (gn_fin_apply)
+bool gn_fin_fusable(const GnFinFuse& f, int dtype, int c0, int c1);
 // run the offered GroupNorm finalize f now if it is pending for d (d->a_gn == its ss)
 int gnfin_flush(const cwdm_conv3d_desc* d, GnFinFuse* f, hipStream_t s);
 
-// conv3d_v5.hip: the warp-specialised conv
-bool v5_eligible(const cwdm_conv3d_desc* d, bool gn, const ConvCall& c);
-int v5_aa_units(const cwdm_conv3d_desc* d, const ConvCall& c, int* lead);
+// conv3d_v5.hip: what of the warp-specialised conv's rules depends on its launch grids.  Both assume
+// a conv that kernel takes (conv_route asks them after its own shape rule).
+// apply-ahead: the per-chunk share (1..8 steps of 256 lanes) its sweep needs and the sweep lead, or 0
+int v5_aa_units(const cwdm_conv3d_desc* d, int* lead);
 // the phase instance takes this upsampling conv (cwdm_conv3d_desc.a_w_phase; rmode: the residual
-// mode after the 1x1 skip pre-pass)
-bool v5_phase_ok(const cwdm_conv3d_desc* d, int rmode, const ConvCall& c);
+// mode the launch sees)
+bool v5_phase_ok(const cwdm_conv3d_desc* d, int rmode, bool stats_wg);
 
-// conv3d_sg.hip: the small-grid conv (fp32x: ConvCall::fp32x)
-bool sg_eligible(const cwdm_conv3d_desc* d, bool fp32x);
-int sg_ksplit(const cwdm_conv3d_desc* d, bool fp32x);
-bool sg_skip_eligible(const cwdm_conv3d_desc* d, bool fp32x);
-int sg_skip_ksplit(const cwdm_conv3d_desc* d, bool fp32x);
-int sg_skip_launch(const cwdm_conv3d_desc* d, void* out, void* partial, const ConvCall& c, hipStream_t s);
-int64_t ksplit_slice_voxels(const cwdm_conv3d_desc* d, bool fp32x);
+// conv3d_sg.hip: the small-grid conv (ksplit: ConvRoute::ksplit / skip_ksplit)
+int sg_skip_launch(const cwdm_conv3d_desc* d, void* out, void* partial, int ksplit, const ConvCall& c, hipStream_t s);
 int64_t sg_sync_bytes(int ksplit);
 int64_t plan_sync_bytes();
 // the apply-ahead sweep counters of a sync block (ConvCall::sync)

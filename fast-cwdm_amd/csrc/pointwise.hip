@@ -492,23 +492,9 @@ __global__ void __launch_bounds__(256, 2) pw_split_kernel(PwParams p) {
 
 }  // namespace
 
-// shapes the pointwise kernel takes: a pure 1x1 (segment B only), 16-bit, no
-// residual / statistics, output in the compute dtype, channels in 16s
-bool pw_eligible(const cwdm_conv3d_desc* d) {
-  if (!dtype_half(d->dtype) || d->a_w || !d->b_w || d->res_mode >= 0 || d->stats || d->out_dtype != d->dtype)
-    return false;
-  const int K = d->b_c0 + d->b_c1;
-  if (K % 16 || d->b_c0 % 16 || d->cout % 8 || (d->out1 && d->out_c0 % 4)) return false;
-  return d->B * d->D * d->H * d->W < (1LL << 40);
-}
-
-// the skip dgrad d runs pw_kernel and can take a GapplyFuse (the conditions pw_forward checks)
-bool pw_gapply_ok(const cwdm_conv3d_desc* d) {
-  return !head_eligible(d) && pw_eligible(d) && d->cout % 8 == 0 && (!d->out1 || d->out_c0 % 8 == 0) &&
-         d->D * d->H * d->W >= 256 && !d->bias;
-}
-
-int pw_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s) {
+// a pure 1x1 the route gave to this kernel (conv_route: Pointwise, or a skip product); gapply: it
+// takes c.gapply (ConvRoute::takes_gapply)
+int pw_forward(const cwdm_conv3d_desc* d, ConvCall& c, bool gapply, hipStream_t s) {
   PwParams p{};
   p.V = d->D * d->H * d->W;
   p.rows = d->B * p.V;
@@ -519,8 +505,8 @@ int pw_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s) {
   p.NT = 32 * pick_nf(d->cout);   // the packed layout's rows per channel tile (cwdm_conv3d_pack)
   p.bias = d->bias; p.bias_bs = d->bias_bstride;
   p.out = d->out; p.out1 = d->out1; p.out_c0 = d->out_c0; p.accumulate = d->accumulate;
-  GapplyFuse* g = c.gapply;
-  if (g && !g->used && p.N % 8 == 0 && (!d->out1 || d->out_c0 % 8 == 0) && p.V >= 256 && !d->bias) {
+  if (gapply) {
+    GapplyFuse* g = c.gapply;
     p.gx0 = g->x0; p.gx1 = g->x1; p.gdu = g->du;
     p.gss = g->ss; p.gcoef = g->coef;
     g->used = true;
@@ -556,16 +542,7 @@ int pw_forward(const cwdm_conv3d_desc* d, ConvCall& c, hipStream_t s) {
   return CWDM_OK;
 }
 
-// the accurate fast mode's pure 1x1 (a_w_split marks it: the split weights of
-// the conv this skip belongs to): fp32, no residual / statistics / second output
-bool pw_split_eligible(const cwdm_conv3d_desc* d) {
-  if (d->dtype != CWDM_F32 || !d->a_w_split || d->a_w || !d->b_w || d->res_mode >= 0 || d->stats ||
-      d->out_dtype != CWDM_F32 || d->out1 || d->accumulate)
-    return false;
-  const int K = d->b_c0 + d->b_c1;
-  return K % 16 == 0 && d->b_c0 % 16 == 0 && d->cout % 32 == 0 && d->B * d->D * d->H * d->W < (1LL << 40);
-}
-
+// the accurate fast mode's pure 1x1 (conv_route: a PwSplit skip product)
 int pw_split_forward(const cwdm_conv3d_desc* d, ProfHook* prof, hipStream_t s) {
   PwParams p{};
   p.V = d->D * d->H * d->W;

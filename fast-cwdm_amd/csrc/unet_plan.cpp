@@ -608,10 +608,90 @@ void build(cwdm_unet* u) {
   u->packed_bwd_bytes = bo;
 }
 
+// the accurate fast mode on a small grid: the fp32 conv d (GroupNorm+SiLU'd or plain input, optional 1x1
+// skip) as ONE bf16 small-grid conv over the K-expanded split input [hi | lo | hi] of SiLU(GN(x))
+// (cwdm::split3_prep, chunk-major) against the weights [hi | hi | lo] (cs.xsplit_off): the three
+// products hi.hi + lo.hi + hi.lo of the split kernels, fp32 output and residual.  The 1x1 skip,
+// if any, runs first into an fp32 residual buffer: the same K expansion on the small-grid kernel's
+// 1x1 form (channels-last split of the raw input, cs.xsplit_sk_off), else pw_split.
+// Workspace: x3 (the conv's or the skip's split input) | skip | K-split slices.
+struct XsgPlan {
+  bool ok = false;
+  bool sk_sg = false;        // the skip on the small-grid kernel (sk_ksplit: its K split)
+  bool sk_pw_split = false;  // else: on pw_split (false: through cwdm::conv3d_forward)
+  int sk_ksplit = 1;
+  cwdm_conv3d_desc e{};      // the bf16 desc (pointers filled in by the forward)
+  cwdm_conv3d_desc ek{};     //   and the skip's
+  cwdm::ConvRoute er;        // the route of e's launch: the small-grid kernel and its K split
+  int64_t x3_bytes = 0, skip_bytes = 0, total = 0;
+};
+XsgPlan xsg_plan(const ConvStep& cs, const cwdm_conv3d_desc& d) {
+  XsgPlan x;
+  if (cs.xsplit_off < 0 || d.res_mode > 1 || (d.b_w && d.res_mode >= 0)) return x;
+  const int64_t sv = cs.amode == 1 ? (d.D / 2) * (d.H / 2) * (d.W / 2) : d.D * d.H * d.W;
+  const int C = d.a_c0 + d.a_c1;
+  cwdm_conv3d_desc e = d;
+  e.dtype = CWDM_BF16;
+  e.a_c0 = 3 * C; e.a_c1 = 0; e.a_gn = nullptr; e.a_w_split = nullptr;
+  e.b_c0 = e.b_c1 = 0; e.b_w = nullptr;
+  if (d.b_w) e.res_mode = 0;
+  e.out_dtype = CWDM_F32;
+  // (the forward runs these convs with ConvCall::fp32x set)
+  cwdm::ConvCall cx;
+  cx.fp32x = true;
+  x.er = cwdm::conv_route_prepared(&e, e.res_mode, cx);
+  if (x.er.kernel != cwdm::ConvKernel::SmallGrid) return x;
+  x.e = e;
+  x.x3_bytes = align_up(d.B * sv * 3 * C * 2);
+  x.skip_bytes = d.b_w ? align_up(d.B * d.D * d.H * d.W * d.cout * 4) : 0;
+  // a K-split slice holds the grid's whole 256-voxel statistics bricks
+  const int64_t slice = d.B * cwdm_conv3d_parts(e.dtype, d.D, d.H, d.W, d.cout) * 256 * d.cout * 4;
+  int64_t part = x.er.ksplit > 1 ? x.er.ksplit * slice : 0;
+  if (d.b_w) {
+    // the skip alone: K-expanded on the small-grid kernel's 1x1 form where its weights were packed, else as fp32
+    cwdm_conv3d_desc k = d;
+    k.a0 = k.a1 = nullptr; k.a_c0 = k.a_c1 = 0; k.a_gn = nullptr; k.a_w = nullptr; k.a_mode = 0;
+    k.bias = nullptr; k.bias_bstride = 0; k.stats = nullptr; k.res = nullptr; k.res_mode = -1;
+    k.out_dtype = CWDM_F32;
+    x.sk_pw_split = cwdm::conv_route_skip(&k, cx).skip == cwdm::SkipKernel::PwSplit;
+    k.dtype = CWDM_BF16;
+    k.a_w_split = nullptr;
+    k.b_c0 = 3 * (d.b_c0 + d.b_c1); k.b_c1 = 0; k.b1 = nullptr;
+    const cwdm::ConvRoute kr = cwdm::conv_route_skip(&k, cx);
+    if (cs.xsplit_sk_off >= 0 && kr.skip == cwdm::SkipKernel::SmallGrid) {
+      x.sk_sg = true;
+      x.sk_ksplit = kr.skip_ksplit;
+      x.ek = k;
+      x.x3_bytes = std::max(x.x3_bytes, align_up(d.B * d.D * d.H * d.W * k.b_c0 * 2));
+      if (kr.skip_ksplit > 1) part = std::max(part, kr.skip_ksplit * slice);
+    }
+  }
+  x.total = x.x3_bytes + x.skip_bytes + part;
+  x.ok = true;
+  return x;
+}
+
+// how the forward runs one conv step, decided in layout()
+enum class ConvKind {
+  Plain,       // cwdm::conv3d_forward with the plan's context
+  SkipPass,    // conv1 of a skip block behind the fused GroupNorm + 1x1-skip pass (cwdm::gn_apply_skip)
+  SkipTaken,   // conv2 of that block: its skip product came from conv1's pass, a plain residual here
+  HeadSplit,   // the accurate fast mode's head over the K-expanded split input
+  Xsg          // the accurate fast mode on a small grid (XsgPlan)
+};
+struct ConvPlan {
+  cwdm::ConvRoute route;   // of the conv's shape in the plan's context, nothing offered
+  cwdm::ConvRoute pass;    // SkipPass: of the launch on the pass's activated copy
+  // with an inference-sized workspace / a training-sized one (which keeps the activated inputs)
+  ConvKind kind = ConvKind::Plain, kind_keep = ConvKind::Plain;
+  int xsg = -1;            // Xsg: its XsgPlan in Layout::xsg
+};
+
 struct Layout {
   int64_t temb, ebias, split, split_bytes, sync;
   int64_t skipbuf = 0;          // conv2 residual written by the fused GroupNorm + 1x1-skip pass
-  std::vector<char> skip_fused; // per conv1 with a skip: that pass is used
+  std::vector<ConvPlan> conv;   // per conv step
+  std::vector<XsgPlan> xsg;     // of the convs the accurate fast mode can rearrange on a small grid
   std::vector<int64_t> t_off, s_off, s_parts;
   std::vector<int64_t> ss_off, mr_off;
   int64_t total;
@@ -642,61 +722,16 @@ cwdm_conv3d_desc conv_shape(const cwdm_unet* u, const ConvStep& cs, int64_t B, i
   }
   d.res_mode = cs.rmode;
   d.out_dtype = cs.out < 0 ? CWDM_F32 : u->cfg.dtype;
-  if (cs.wsplit_off >= 0) d.a_w_split = reinterpret_cast<const void*>(1);   // presence flag only
+  if (cs.wsplit_off >= 0) d.a_w_split = reinterpret_cast<const void*>(1);   // presence flags only
+  if (cs.wphase_off >= 0) d.a_w_phase = reinterpret_cast<const void*>(1);
   return d;
 }
 
-// the accurate fast mode on a small grid: the fp32 conv d (GroupNorm+SiLU'd or plain input, optional 1x1
-// skip) as ONE bf16 small-grid conv over the K-expanded split input [hi | lo | hi] of SiLU(GN(x))
-// (cwdm::split3_prep, chunk-major) against the weights [hi | hi | lo] (cs.xsplit_off): the three
-// products hi.hi + lo.hi + hi.lo of the split kernels, fp32 output and residual.  The 1x1 skip,
-// if any, runs first into an fp32 residual buffer: the same K expansion on the small-grid kernel's
-// 1x1 form (channels-last split of the raw input, cs.xsplit_sk_off), else pw_split.
-// Workspace: x3 (the conv's or the skip's split input) | skip | K-split slices.
-struct XsgPlan {
-  bool ok = false;
-  bool sk_sg = false;     // the skip on the small-grid kernel
-  cwdm_conv3d_desc e{};   // the bf16 desc (pointers filled in by the forward)
-  cwdm_conv3d_desc ek{};  //   and the skip's
-  int64_t x3_bytes = 0, skip_bytes = 0, total = 0;
-};
-XsgPlan xsg_plan(const cwdm_unet* u, const ConvStep& cs, const cwdm_conv3d_desc& d) {
-  XsgPlan x;
-  if (cs.xsplit_off < 0 || d.res_mode > 1 || (d.b_w && d.res_mode >= 0)) return x;
-  const int64_t sv = cs.amode == 1 ? (d.D / 2) * (d.H / 2) * (d.W / 2) : d.D * d.H * d.W;
-  const int C = d.a_c0 + d.a_c1;
-  cwdm_conv3d_desc e = d;
-  e.dtype = CWDM_BF16;
-  e.a_c0 = 3 * C; e.a_c1 = 0; e.a_gn = nullptr; e.a_w_split = nullptr;
-  e.b_c0 = e.b_c1 = 0; e.b_w = nullptr;
-  if (d.b_w) e.res_mode = 0;
-  e.out_dtype = CWDM_F32;
-  // (the forward runs these convs with ConvCall::fp32x set)
-  if (!cwdm::sg_eligible(&e, true)) return x;
-  x.e = e;
-  x.x3_bytes = align_up(d.B * sv * 3 * C * 2);
-  x.skip_bytes = d.b_w ? align_up(d.B * d.D * d.H * d.W * d.cout * 4) : 0;
-  const int S = cwdm::sg_ksplit(&e, true);
-  int64_t part = S > 1 ? (int64_t)S * d.B * cwdm::ksplit_slice_voxels(&e, true) * d.cout * 4 : 0;
-  if (d.b_w && cs.xsplit_sk_off >= 0) {
-    cwdm_conv3d_desc k = d;
-    k.dtype = CWDM_BF16;
-    k.a0 = k.a1 = nullptr; k.a_c0 = k.a_c1 = 0; k.a_gn = nullptr; k.a_w = nullptr; k.a_w_split = nullptr; k.a_mode = 0;
-    k.b_c0 = 3 * (d.b_c0 + d.b_c1); k.b_c1 = 0; k.b1 = nullptr;
-    k.bias = nullptr; k.bias_bstride = 0; k.stats = nullptr; k.res = nullptr; k.res_mode = -1;
-    k.out_dtype = CWDM_F32;
-    if (cwdm::sg_skip_eligible(&k, true)) {
-      x.sk_sg = true;
-      x.ek = k;
-      x.x3_bytes = std::max(x.x3_bytes, align_up(d.B * d.D * d.H * d.W * k.b_c0 * 2));
-      const int Sk = cwdm::sg_skip_ksplit(&k, true);
-      if (Sk > 1) part = std::max(part, (int64_t)Sk * d.B * cwdm::ksplit_slice_voxels(&k, true) * d.cout * 4);
-    }
-  }
-  x.total = x.x3_bytes + x.skip_bytes + part;
-  (void)u;
-  x.ok = true;
-  return x;
+// statistics partial rows per tensor: the per-tile layout, or the rows of a warp-specialised conv
+// that summed them per workgroup (ConvCall::stats_rows; env CWDM_STATS_WG=0: per tile everywhere)
+bool plan_stats_wg() {
+  static const bool on = env_not0("CWDM_STATS_WG");
+  return on;
 }
 
 Layout layout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) {
@@ -725,42 +760,68 @@ Layout layout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) {
   }
   for (const auto& g : u->gns) L.ss_off.push_back(take(B * (int64_t)g.channels * 2 * 4));
   for (size_t i = 0; i < u->gns.size(); ++i) L.mr_off.push_back(take(B * (int64_t)u->cfg.num_groups * 2 * 4));
+  // every conv's route, once: what the forward runs and what the regions below are sized for
+  const size_t nc = u->convs.size();
+  L.conv.resize(nc);
+  cwdm::ConvCall lc;
+  lc.stats_wg = plan_stats_wg();
   int64_t split = 0;
-  for (const auto& cs : u->convs) {
-    cwdm_conv3d_desc d = conv_shape(u, cs, B, D, H, W);
-    const int64_t n = cwdm_conv3d_workspace_bytes(&d);
-    if (n > split) split = n;
-    const XsgPlan xp = xsg_plan(u, cs, d);
-    if (xp.ok && xp.total > split) split = xp.total;
+  for (size_t i = 0; i < nc; ++i) {
+    const auto& cs = u->convs[i];
+    const cwdm_conv3d_desc d = conv_shape(u, cs, B, D, H, W);
+    ConvPlan& cp = L.conv[i];
+    cp.route = cwdm::conv_route(&d, lc);
+    split = std::max(split, cwdm::conv_workspace_bytes(&d, cp.route));
+    if (cs.xsplit_off < 0) continue;
+    const XsgPlan xp = xsg_plan(cs, d);
+    if (!xp.ok) continue;
+    split = std::max(split, xp.total);
+    cp.xsg = (int)L.xsg.size();
+    L.xsg.push_back(xp);
   }
   L.split_bytes = split;
   L.split = take(split);
   // ResBlocks with a 1x1 skip whose convs run on the DMA kernel: GN1 and the
-  // skip read x in one pass (cwdm::gn_apply_skip)
-  L.skip_fused.assign(u->convs.size(), 0);
+  // skip read x in one pass (cwdm::gn_apply_skip).  A conv1 that applies GroupNorm
+  // in its own LDS (conv3d_v5, inference) reads x raw: the pass would only write an
+  // activated copy nobody reads; conv2 then runs the 1x1 skip itself
   int64_t skipb = 0;
   const bool fuse = env_not0("CWDM_SKIP_FUSE");  // "0": A/B switch for the fused pass (read per plan)
-  for (size_t i = 0; fuse && i < u->convs.size(); ++i) {
+  for (size_t i = 0; fuse && i < nc; ++i) {
     const auto& c1 = u->convs[i];
     if (c1.skip_conv < 0 || c1.gn < 0 || c1.amode != 0) continue;
     const auto& c2 = u->convs[c1.skip_conv];
-    cwdm_conv3d_desc d1 = conv_shape(u, c1, B, D, H, W), d2 = conv_shape(u, c2, B, D, H, W);
+    const cwdm_conv3d_desc d1 = conv_shape(u, c1, B, D, H, W);
     const int64_t vpb = d1.D * d1.H * d1.W;
-    if (!cwdm::v4_eligible(&d1, cwdm::ConvCall{}) || !cwdm::v4_eligible(&d2, cwdm::ConvCall{}) ||
+    ConvPlan& cp = L.conv[i];
+    if (!cp.route.v4_ok || !L.conv[c1.skip_conv].route.v4_ok ||
         !cwdm::apply_skip_ok(u->cfg.dtype, c1.cin_a, c2.cout, B, vpb))
       continue;
-    L.skip_fused[i] = 1;
+    cp.kind_keep = ConvKind::SkipPass;
+    if (!cp.route.gn_in_lds()) cp.kind = ConvKind::SkipPass;
+    cp.pass = cwdm::conv_route_prepared(&d1, d1.res_mode, lc);
     skipb = std::max(skipb, B * vpb * c2.cout * es);
   }
   L.skipbuf = take(skipb);
-  L.total = off;
-  L.keep_off.assign(u->convs.size(), -1);
-  for (size_t i = 0; i < u->convs.size(); ++i) {
+  for (size_t i = 0; i < nc; ++i) {
     const auto& cs = u->convs[i];
-    cwdm_conv3d_desc d = conv_shape(u, cs, B, D, H, W);
-    if (!dtype_half(u->cfg.dtype) || cs.gn < 0 || cs.amode > 1 || cs.s2 || cwdm::head_eligible(&d) ||
-        !cwdm::v4_eligible(&d, cwdm::ConvCall{}))
-      continue;
+    ConvPlan& cp = L.conv[i];
+    if (cp.kind_keep == ConvKind::SkipPass) continue;
+    const bool after_c1 = cs.ws_p >= 0 && i > 0 && u->convs[i - 1].skip_conv == (int)i;
+    if (after_c1 && L.conv[i - 1].kind_keep == ConvKind::SkipPass) cp.kind_keep = ConvKind::SkipTaken;
+    // (the accurate fast mode's rearranged convs: inference only, and never a conv2 of a fused pass --
+    // that pass needs the wide grids, these the output head and the small ones)
+    const cwdm_conv3d_desc d = conv_shape(u, cs, B, D, H, W);
+    if (after_c1 && L.conv[i - 1].kind == ConvKind::SkipPass) cp.kind = ConvKind::SkipTaken;
+    else if (cs.hsplit_off >= 0 && cs.gn >= 0 && B * d.D * d.H * d.W * 3 * d.a_c0 * 2 <= split) cp.kind = ConvKind::HeadSplit;
+    else if (cp.xsg >= 0 && L.xsg[cp.xsg].total <= split) cp.kind = ConvKind::Xsg;
+  }
+  L.total = off;
+  L.keep_off.assign(nc, -1);
+  for (size_t i = 0; i < nc; ++i) {
+    const auto& cs = u->convs[i];
+    if (!dtype_half(u->cfg.dtype) || cs.gn < 0 || cs.amode > 1 || cs.s2 || !L.conv[i].route.v4_ok) continue;
+    const cwdm_conv3d_desc d = conv_shape(u, cs, B, D, H, W);
     const int64_t sv = cs.amode == 1 ? (d.D / 2) * (d.H / 2) * (d.W / 2) : d.D * d.H * d.W;
     const int64_t cin = d.a_c0 + d.a_c1;
     if (sv * cin * 2 >= (1LL << 31)) continue;  // the DMA wgrad's per-batch buffer range
@@ -1035,7 +1096,6 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
     return wb + L.t_off[id];
   };
   int conv_i = 0;
-  const int es = esize(u->cfg.dtype);
   if (u->profiling) {
     const size_t need = u->convs.size() * 4;
     while (u->ev.size() < need) {
@@ -1054,9 +1114,7 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
   // first).  A pending one whose consumer is not the next step runs on its own.
   // Env CWDM_GNFIN=0: every finalize as its own launch (A/B switch).
   static const bool fin_on = env_not0("CWDM_GNFIN");
-  // statistics partial rows per tensor: the per-tile layout, or the rows of a warp-specialised conv
-  // that summed them per workgroup (ConvCall::stats_rows; env CWDM_STATS_WG=0: per tile everywhere)
-  static const bool stats_wg = env_not0("CWDM_STATS_WG");
+  // statistics partial rows per tensor: the per-tile layout, or a conv's per-workgroup rows (plan_stats_wg)
   std::vector<int64_t> srows(L.s_parts);
   int fin_pend = -1;
   auto fin_args = [&](int gi, cwdm::GnFinFuse& f) {
@@ -1155,40 +1213,38 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
     // this conv's context: the plan's zeroed sync block, per-workgroup statistics, the profiling hook
     cwdm::ConvCall cc;
     cc.sync = reinterpret_cast<unsigned*>(wb + L.sync);
-    cc.stats_wg = stats_wg;
+    cc.stats_wg = plan_stats_wg();
     if (u->profiling) cc.prof = &u->hooks[conv_i];
-    // a skip block's conv1 that applies GroupNorm in its own LDS (conv3d_v5,
-    // inference) reads x raw: the fused GroupNorm + 1x1-skip pass would only
-    // write an activated copy nobody reads; conv2 then runs the 1x1 skip itself
-    auto skip_pass_at = [&](int ci) {
-      if (!L.skip_fused[ci]) return false;
-      if (keep) return true;
-      const cwdm_conv3d_desc dc = conv_shape(u, u->convs[ci], B, D, H, W);
-      return !cwdm::v5_eligible(&dc, true, cwdm::ConvCall{});
-    };
-    if (skip_pass_at(st.idx)) {
-      // conv1 of a skip block: SiLU(GN1(x)) for this conv and W_skip . x for conv2 in one pass
-      const auto& c2 = u->convs[cs.skip_conv];
-      const int64_t vpb = d.D * d.H * d.W;
-      void* act = keep && L.keep_off[st.idx] >= 0 ? wb + L.keep_off[st.idx] : wb + L.split;
+    const ConvPlan& cp = L.conv[st.idx];
+    ConvKind kind = keep ? cp.kind_keep : cp.kind;
+    if (kind == ConvKind::SkipTaken) {
+      // the skip was computed in conv1's GroupNorm pass: a plain residual here
+      d.b0 = d.b1 = nullptr; d.b_c0 = d.b_c1 = 0; d.b_w = nullptr;
+      d.res = wb + L.skipbuf; d.res_mode = 0;
+      kind = ConvKind::Plain;
+    }
+    // (the output head fuses the sampling step where the step's arguments allow: a run-time question)
+    const bool head_samp = kind != ConvKind::SkipPass && samp && cs.out < 0 && cwdm::head_sampler_eligible(&d, samp);
+    if (head_samp) {
       if ((rc = flush_fin())) return rc;
-      if ((rc = cwdm::gn_apply_skip(d.a0, d.a_c0, d.a1, d.a_c1, d.a_gn, B, vpb, u->cfg.dtype, pk + c2.wsk_off,
-                                    c2.cout, act, wb + L.skipbuf, s)))
-        return rc;
-      void* part = wb + L.split + ((B * vpb * (d.a_c0 + d.a_c1) * es + 255) & ~(int64_t)255);
-      if ((rc = cwdm::v4_launch(&d, act, d.a_c0 + d.a_c1, nullptr, 0, 1, d.res, d.res_mode, part, cc, s))) return rc;
-    } else {
-      if (cs.ws_p >= 0 && st.idx > 0 && u->convs[st.idx - 1].skip_conv == st.idx && skip_pass_at(st.idx - 1)) {
-        // the skip was computed in conv1's GroupNorm pass: a plain residual here
-        d.b0 = d.b1 = nullptr; d.b_c0 = d.b_c1 = 0; d.b_w = nullptr;
-        d.res = wb + L.skipbuf; d.res_mode = 0;
-      }
-      const int64_t x3_bytes = B * d.D * d.H * d.W * 3 * d.a_c0 * 2;
-      if (samp && cs.out < 0 && cwdm::head_sampler_eligible(&d, samp)) {
+      if ((rc = cwdm::head_sampler_forward(&d, samp, cc.prof, s))) return rc;
+      if (fused) *fused = 1;
+    } else switch (kind) {
+      case ConvKind::SkipPass: {
+        // conv1 of a skip block: SiLU(GN1(x)) for this conv and W_skip . x for conv2 in one pass
+        const auto& c2 = u->convs[cs.skip_conv];
+        const int64_t vpb = d.D * d.H * d.W;
+        void* act = keep && L.keep_off[st.idx] >= 0 ? wb + L.keep_off[st.idx] : wb + L.split;
         if ((rc = flush_fin())) return rc;
-        if ((rc = cwdm::head_sampler_forward(&d, samp, cc.prof, s))) return rc;
-        if (fused) *fused = 1;
-      } else if (cs.hsplit_off >= 0 && !keep && d.a_gn && x3_bytes <= L.split_bytes) {
+        if ((rc = cwdm::gn_apply_skip(d.a0, d.a_c0, d.a1, d.a_c1, d.a_gn, B, vpb, u->cfg.dtype, pk + c2.wsk_off,
+                                      c2.cout, act, wb + L.skipbuf, s)))
+          return rc;
+        void* part = wb + L.split + cp.route.ws_act;   // (the K-split slices follow the activated input)
+        if ((rc = cwdm::v4_launch(&d, act, d.a_c0 + d.a_c1, nullptr, 0, 1, d.res, d.res_mode, part, cp.pass, cc, s)))
+          return rc;
+        break;
+      }
+      case ConvKind::HeadSplit: {
         // the accurate fast mode's head: a bf16 head over the K-expanded split input (head_split3_prep)
         if ((rc = flush_fin())) return rc;
         void* x3 = wb + L.split;
@@ -1201,8 +1257,11 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
         e.a_gn = nullptr; e.a_w = pk + cs.hsplit_off; e.a_w_split = nullptr;
         e.workspace = nullptr; e.ws_bytes = 0;
         if ((rc = cwdm::conv3d_forward(&e, cc, s))) return rc;
-      } else if (XsgPlan xp = keep ? XsgPlan{} : xsg_plan(u, cs, d); xp.ok && xp.total <= L.split_bytes) {
+        break;
+      }
+      case ConvKind::Xsg: {
         // the accurate fast mode on a small grid: one bf16 small-grid conv over the K-expanded split input
+        const XsgPlan& xp = L.xsg[cp.xsg];
         if ((rc = flush_fin())) return rc;
         unsigned char* x3 = wb + L.split;
         const void* res = d.res;
@@ -1216,8 +1275,8 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
             return rc;
           cwdm_conv3d_desc k = xp.ek;
           k.b0 = x3; k.b_w = pk + cs.xsplit_sk_off;
-          void* kpart = cwdm::sg_skip_ksplit(&k, cc.fp32x) > 1 ? part : nullptr;
-          if ((rc = cwdm::sg_skip_launch(&k, x3 + xp.x3_bytes, kpart, cc, s))) return rc;
+          if ((rc = cwdm::sg_skip_launch(&k, x3 + xp.x3_bytes, xp.sk_ksplit > 1 ? part : nullptr, xp.sk_ksplit, cc, s)))
+            return rc;
           res = x3 + xp.x3_bytes; rmode = 0;
         } else if (d.b_w) {
           // the 1x1 skip first, into an fp32 residual (pw_split: the split products of the 1x1 weights)
@@ -1226,8 +1285,7 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
           k.bias = nullptr; k.bias_bstride = 0; k.stats = nullptr; k.res = nullptr; k.res_mode = -1;
           k.out = x3 + xp.x3_bytes; k.out_dtype = CWDM_F32;
           k.workspace = nullptr; k.ws_bytes = 0;
-          if ((rc = cwdm::pw_split_eligible(&k) ? cwdm::pw_split_forward(&k, cc.prof, s)
-                                                : cwdm::conv3d_forward(&k, cc, s)))
+          if ((rc = xp.sk_pw_split ? cwdm::pw_split_forward(&k, cc.prof, s) : cwdm::conv3d_forward(&k, cc, s)))
             return rc;
           res = k.out; rmode = 0;
         }
@@ -1241,9 +1299,11 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
         e.res = res; e.res_mode = rmode;
         e.out = d.out; e.stats = d.stats;
         e.workspace = nullptr; e.ws_bytes = 0;
-        if (cwdm::sg_ksplit(&e, cc.fp32x) <= 1) part = nullptr;
-        if ((rc = cwdm::v4_launch(&e, x3, e.a_c0, nullptr, 0, 1, res, rmode, part, cc, s))) return rc;
-      } else {
+        if (xp.er.ksplit <= 1) part = nullptr;
+        if ((rc = cwdm::v4_launch(&e, x3, e.a_c0, nullptr, 0, 1, res, rmode, part, xp.er, cc, s))) return rc;
+        break;
+      }
+      default: {
         cc.act_keep = keep && L.keep_off[st.idx] >= 0 ? wb + L.keep_off[st.idx] : nullptr;
         cwdm::GnFinFuse ff{};
         const bool offer = fin_pend >= 0 && d.a_gn == reinterpret_cast<const float*>(wb + L.ss_off[u->gns[fin_pend].ss_id]);
@@ -1803,7 +1863,7 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
       // 1x1 skip dgrad into dx0 / dx1 (dual output); with skip_gapply the
       // GroupNorm-1 backward's apply pass rides in its epilogue (GapplyFuse),
       // so it runs after GN1's reduce / finalize below
-      auto skip_dgrad = [&](cwdm::GapplyFuse* gf, bool dry) -> int {
+      auto skip_dgrad_desc = [&]() {
         const int c0 = u->tensors[c2.sb0].channels, cc1 = c2.sb1 >= 0 ? u->tensors[c2.sb1].channels : 0;
         cwdm_conv3d_desc d{};
         d.dtype = dt; d.B = B; d.D = D >> lout; d.H = H >> lout; d.W = W >> lout;
@@ -1812,7 +1872,18 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
         d.res_mode = -1;
         d.out = grd(c2.sb0); d.out_dtype = dt;
         if (c2.sb1 >= 0) { d.out1 = grd(c2.sb1); d.out_c0 = c0; }
-        if (dry) return pw_gapply_ok(&d) ? 1 : 0;
+        return d;
+      };
+      // (its route would take an offered apply)
+      auto skip_takes_gapply = [&]() {
+        const cwdm_conv3d_desc d = skip_dgrad_desc();
+        cwdm::GapplyFuse probe{};
+        cwdm::ConvCall cc;
+        cc.gapply = &probe;
+        return cwdm::conv_route(&d, cc).takes_gapply;
+      };
+      auto skip_dgrad = [&](cwdm::GapplyFuse* gf) -> int {
+        cwdm_conv3d_desc d = skip_dgrad_desc();
         // equalise the store/accumulate state of the two outputs
         int a0 = take_acc(c2.sb0), a1 = c2.sb1 >= 0 ? take_acc(c2.sb1) : a0;
         if (a0 != a1) {
@@ -1832,12 +1903,12 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
       };
       static const bool gapply_on = env_not0("CWDM_GAPPLY_FUSE");
       const bool skip_gapply = c2.ws_p >= 0 && gapply_on && bk.updown == 0 && c2.sb0 == bk.x0 &&
-                               c2.sb1 == bk.x1 && skip_dgrad(nullptr, true) == 1;
+                               c2.sb1 == bk.x1 && skip_takes_gapply();
       if (c2.ws_p >= 0) {
         const int c0 = u->tensors[c2.sb0].channels, cc1 = c2.sb1 >= 0 ? u->tensors[c2.sb1].channels : 0;
         if ((rc = wgrad(lout, 1, act(c2.sb0), c0, act(c2.sb1), cc1, 0, nullptr, grd(o), cout, cout, GR(c2.ws_p))))
           return rc;
-        if (!skip_gapply && (rc = skip_dgrad(nullptr, false))) return rc;
+        if (!skip_gapply && (rc = skip_dgrad(nullptr))) return rc;
       } else {
         // identity residual (possibly through the block's resampling)
         const int xt = bk.x0;
@@ -1902,7 +1973,7 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
           return rc;
         cwdm::GapplyFuse gf{};
         gf.x0 = act(bk.x0); gf.x1 = act(bk.x1); gf.du = tmp; gf.ss = ss_of(bk.g1); gf.coef = coef;
-        if ((rc = skip_dgrad(&gf, false))) return rc;
+        if ((rc = skip_dgrad(&gf))) return rc;
         if ((rc = avg_bwd())) return rc;
         continue;
       }

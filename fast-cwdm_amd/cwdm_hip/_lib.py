@@ -157,6 +157,7 @@ _PROTOS = {
     "cwdm_debug_v5_aa": (ctypes.c_int, [ctypes.c_int]),
     "cwdm_debug_up_phase": (ctypes.c_int, [ctypes.c_int]),
     "cwdm_debug_stats_wg": (i64, [ctypes.c_int]),
+    "cwdm_debug_conv_route": (ctypes.c_int, [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     "cwdm_debug_v5_aa_timeout": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "cwdm_device_status": (ctypes.c_int, [ctypes.c_int]),
     "cwdm_debug_gn_fin_apply": (ctypes.c_int, [vp, i64, ctypes.c_int, vp, i64, ctypes.c_int, vp, vp, ctypes.c_int,

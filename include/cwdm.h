@@ -423,6 +423,25 @@ int cwdm_debug_up_phase(int on);
  * nothing, returns the rows the last launch of this thread wrote that way (0: per tile). */
 int64_t cwdm_debug_stats_wg(int on);
 
+/* Diagnostics / tests only: the route a lone cwdm_conv3d_forward(d) of this thread
+ * would take, decided as that call decides it (the default context plus the
+ * cwdm_debug_stats_wg state; the brick kernels where d->ws_bytes is below the
+ * preferred route's workspace).  The desc's pointers are read as presence flags
+ * only; nothing is launched and no device is needed (without one: 256 CUs).
+ * Writes n >= 6 ints:
+ *   out[0] kernel: 0 head, 1 pointwise, 2 small-grid, 3 warp-specialised phase
+ *          instance, 4 warp-specialised, 5 warp-specialised with GroupNorm in LDS,
+ *          6 warp-specialised apply-ahead, 7 split-bf16 (fp32 with a_w_split),
+ *          8 DMA-staged (v4), 9 brick / split-K
+ *   out[1] GroupNorm input: 0 none, 1 cwdm_gn_apply pre-pass, 2 the pre-pass that
+ *          also finalizes (never for a lone call), 3 in the kernel
+ *   out[2] 1x1 skip product beside a 3x3x3 conv: 0 none, 1 small-grid, 2 pointwise,
+ *          3 split-bf16 pointwise, 4 brick
+ *   out[3] K split of the conv    out[4] apply-ahead share (0: none)
+ *   out[5] workspace bytes of the route (saturated at INT_MAX; 0 for the brick
+ *          kernels, whose own split-K size is in cwdm_conv3d_workspace_bytes) */
+int cwdm_debug_conv_route(const cwdm_conv3d_desc* d, int* out, int n);
+
 /* Diagnostics / tests only: make every apply-ahead counter wait require `extra`
  * arrivals beyond the grid and give up after `spin` s_sleep rounds (0, 0 =
  * defaults: no extra, 1 << 24 rounds) -- forces the timeout path, which must
