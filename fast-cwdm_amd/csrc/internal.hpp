@@ -163,6 +163,19 @@ int gn_silu_bwd_impl(const void* x0, int c0, const void* x1, int c1, const void*
                      int64_t ws_bytes, float* chs, int64_t chs_stride, cwdm_stream_t stream, int acc_affine,
                      const float* pre_part = nullptr, int pre_nblk = 0, const float** coef_out = nullptr);
 int gb_part_reduce(const float* part, int nblk, int C, int64_t B, int slices, float* out, hipStream_t s);
+// attention.hip: the bottleneck attention block's projections (cwdm_attn_linear / cwdm_attn_pack with
+// their arguments spelled out), the adjoint of the legacy row permutation for the qkv gradients
+// (dst[source row][c] += src[packed row][c]), and the backward of a GroupNorm without activation:
+// dx = (acc ? dx : 0) + add + dGN(dn), dgamma / dbeta accumulated; part: fp32 scratch [B][C][2]
+int64_t attn_parts(int64_t T);
+int attn_linear(int dtype, int64_t B, int64_t T, int K, int N, const void* in, const float* gn, const void* w,
+                const float* bias, const void* res, void* out, void* n_out, float* stats, hipStream_t s);
+int attn_pack(const float* w, int rows, int cols, int heads, int ch, int legacy, int transpose, int dtype, void* out,
+              hipStream_t s);
+int attn_unperm_add(const float* src, float* dst, int rows, int cols, int heads, int ch, hipStream_t s);
+int gn_lin_bwd(int dtype, int64_t B, int64_t T, int C, int groups, const void* x, const void* dn, const float* mr,
+               const float* gamma, const void* add, void* dx, int acc, float* part, float* dgamma, float* dbeta,
+               hipStream_t s);
 // wavelet_nd.hip
 int haar_nd_synth_add(int dtype, int64_t B, int64_t d, int64_t h, int64_t w, int C, const void* L, int64_t l_vs,
                       float lll, const void* H, int64_t h_vs, float high, void* fine, int acc, hipStream_t s);

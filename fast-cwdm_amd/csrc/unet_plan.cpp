@@ -26,7 +26,8 @@ struct Param { std::string name; std::vector<int64_t> shape; int64_t numel() con
 struct Tensor {
   int level, channels;
   int stats_kind = 0;  // producer of its (sum, sum^2) parts: 0 conv epilogue, 1 / 2 cwdm_haar_nd over its own /
-                       // the half grid (analysis / synthesis output), 3 cwdm_skip_avg, -1 none (never GroupNorm'd)
+                       // the half grid (analysis / synthesis output), 3 cwdm_skip_avg, 4 cwdm_attn_linear (one row
+                       // per 16 voxels), -1 none (never GroupNorm'd)
 };
 
 struct GnStep {
@@ -85,7 +86,17 @@ struct AvgStep {  // additive skip (cwdm_skip_avg, skip_avg.hip): out = (a + b) 
   int a, b, out, level, channels;
 };
 
-enum StepKind { kGn, kConv, kPool /* pre-pass */, kS2d /* space-to-depth */, kHaar, kAvg /* additive skip */ };
+// the bottleneck AttentionBlock (attention.hip): out = src + proj_out(attention(qkv(GroupNorm(src))))
+struct AttnStep {
+  int src, out, gn, level;      // tensors, the norm's scale/shift buffer
+  int C, heads, ch;
+  int qkv_w_p, qkv_b_p, proj_w_p, proj_b_p;                   // param indices
+  int64_t qkv_w_off, qkv_b_off, proj_w_off, proj_b_off;       // packed byte offsets ([Q | K | V] row order)
+  int64_t qkvT_off = -1, projT_off = -1;                      // packed_bwd: the transposed weights (input gradients)
+};
+
+enum StepKind { kGn, kConv, kPool /* pre-pass */, kS2d /* space-to-depth */, kHaar, kAvg /* additive skip */,
+                kAttn /* bottleneck attention */ };
 struct Step { StepKind kind; int idx; };
 
 // one ResBlock, for the backward (reverse order) and the gradient segments
@@ -95,7 +106,8 @@ struct Block {
   int updown;                 // 0 none, 1 up, 2 down; layers without a ResBlock (resblock_updown=False):
                               // 3 Downsample stride-2 conv (c1, pool = its S2dStep), 4 Upsample nearest + conv (c1);
                               // WavUNetModel ResBlocks: 5 down (DWT), 6 up (IDWT); 7 WaveletDownsample of the input
-                              // pyramid (pool = its HaarStep, c1 = its conv, x0 = the pyramid level it transforms)
+                              // pyramid (pool = its HaarStep, c1 = its conv, x0 = the pyramid level it transforms);
+                              // 8 the bottleneck AttentionBlock (pool = its AttnStep, g1 = its norm, x0 = its input)
   int p_begin, p_end;         // parameter index range
   int emb_k;                  // index into emb_rows_*
   int hh = -1, hx = -1;       // WavUNetModel down / up blocks: HaarSteps of h (+ emb) and of x (x_upd)
@@ -129,6 +141,7 @@ struct cwdm_unet {
   std::vector<S2dStep> s2ds;
   std::vector<HaarStep> haars;
   std::vector<AvgStep> avgs;
+  std::vector<AttnStep> attns;
   std::vector<Step> steps;
   struct Alias { std::string name; int owner, before; };
   std::vector<Alias> aliases;     // WavUNetModel: second state_dict name of a reused parameter; before = the
@@ -497,7 +510,31 @@ void build(cwdm_unet* u) {
   if (!c.use_freq) {
     h = resblock("middle_block.0", h, -1, ch, 0);
     u->trace.push_back(h); u->trace_level.push_back(level);
-    h = resblock("middle_block.1", h, -1, ch, 0);
+    if (c.bottleneck_attention) {
+      // AttentionBlock (unet.py:314-360): norm, qkv, proj_out in state_dict order; the ResBlock after it
+      // is then middle_block.2
+      Block blk{};
+      blk.p_begin = (int)u->params.size();
+      blk.x0 = h; blk.x1 = -1; blk.updown = 8; blk.c1 = blk.c2 = blk.g2 = -1; blk.emb_k = -1;
+      AttnStep at{};
+      at.src = h; at.level = level; at.C = ch;
+      at.heads = c.num_head_channels > 0 ? ch / c.num_head_channels : std::max(c.num_heads, 1);
+      at.ch = ch / at.heads;
+      blk.g1 = at.gn = gn_step("middle_block.1.norm", h, -1, level);
+      at.qkv_w_p = addp("middle_block.1.qkv.weight", {3 * ch, ch, 1});
+      at.qkv_b_p = addp("middle_block.1.qkv.bias", {3 * ch});
+      at.proj_w_p = addp("middle_block.1.proj_out.weight", {ch, ch, 1});
+      at.proj_b_p = addp("middle_block.1.proj_out.bias", {ch});
+      h = at.out = new_tensor(level, ch);
+      u->tensors[h].stats_kind = 4;
+      u->attns.push_back(at);
+      u->steps.push_back({kAttn, (int)u->attns.size() - 1});
+      blk.pool = (int)u->attns.size() - 1;
+      blk.p_end = (int)u->params.size();
+      u->blocks.push_back(blk);
+      u->trace.push_back(h); u->trace_level.push_back(level);
+    }
+    h = resblock(c.bottleneck_attention ? "middle_block.2" : "middle_block.1", h, -1, ch, 0);
     u->trace.push_back(h); u->trace_level.push_back(level);
     idx = 0;
   }
@@ -588,6 +625,13 @@ void build(cwdm_unet* u) {
     gs.gamma_off = take((int64_t)gs.channels * 4);
     gs.beta_off = take((int64_t)gs.channels * 4);
   }
+  const int64_t es_w = dtype_size(c.dtype);
+  for (auto& at : u->attns) {
+    at.qkv_w_off = take((int64_t)3 * at.C * at.C * es_w);
+    at.qkv_b_off = take((int64_t)3 * at.C * 4);
+    at.proj_w_off = take((int64_t)at.C * at.C * es_w);
+    at.proj_b_off = take((int64_t)at.C * 4);
+  }
   if (split3_max > 0) u->split3_tmp = take(split3_max);
   u->packed_bytes = off;
 
@@ -604,6 +648,10 @@ void build(cwdm_unet* u) {
     const int cpad = (int)((cs.cout + ck - 1) / ck * ck);
     u->dg_off.push_back(i == 0 ? -1 : takeb(cwdm_conv3d_packed_bytes(cs.cin_a, cpad, 3, c.dtype)));
     u->dgs_off.push_back(cs.ws_p >= 0 ? takeb(cwdm_conv3d_packed_bytes(cs.cin_b, cpad, 1, c.dtype)) : -1);
+  }
+  for (auto& at : u->attns) {
+    at.qkvT_off = takeb((int64_t)3 * at.C * at.C * es_w);
+    at.projT_off = takeb((int64_t)at.C * at.C * es_w);
   }
   u->packed_bwd_bytes = bo;
 }
@@ -699,6 +747,9 @@ struct Layout {
   // whose forward pre-pass writes one, kept past the inference total for the
   // DMA-staged wgrad (cwdm_unet_train_workspace_bytes); -1 = not kept
   std::vector<int64_t> keep_off;
+  // the attention block: its qkv projection (B, T, 3 C) and attention output (B, T, C); a training-sized
+  // workspace also keeps the rows' log-sum-exp (fp32 [B][heads][T]) and the normalised input (B, T, C)
+  int64_t attn_qkv = -1, attn_a = -1, attn_L = -1, attn_n = -1;
   int64_t train_total;
 };
 
@@ -754,6 +805,7 @@ Layout layout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) {
                           : t.stats_kind == 1 ? cwdm_haar_nd_parts(d, h, w)
                           : t.stats_kind == 2 ? cwdm_haar_nd_parts(d / 2, h / 2, w / 2)
                           : t.stats_kind == 3 ? cwdm_skip_avg_parts(d * h * w)
+                          : t.stats_kind == 4 ? cwdm::attn_parts(d * h * w)
                                               : cwdm_conv3d_parts(u->cfg.dtype, d, h, w, t.channels);
     L.s_parts.push_back(parts);
     L.s_off.push_back(take(B * parts * t.channels * 2 * 4));
@@ -803,6 +855,11 @@ Layout layout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) {
     skipb = std::max(skipb, B * vpb * c2.cout * es);
   }
   L.skipbuf = take(skipb);
+  for (const auto& at : u->attns) {
+    const int64_t T = (D >> at.level) * (H >> at.level) * (W >> at.level);
+    L.attn_qkv = take(B * T * 3 * at.C * es);
+    L.attn_a = take(B * T * at.C * es);
+  }
   for (size_t i = 0; i < nc; ++i) {
     const auto& cs = u->convs[i];
     ConvPlan& cp = L.conv[i];
@@ -826,6 +883,11 @@ Layout layout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) {
     const int64_t cin = d.a_c0 + d.a_c1;
     if (sv * cin * 2 >= (1LL << 31)) continue;  // the DMA wgrad's per-batch buffer range
     L.keep_off[i] = take(B * sv * cin * es);
+  }
+  for (const auto& at : u->attns) {
+    const int64_t T = (D >> at.level) * (H >> at.level) * (W >> at.level);
+    L.attn_L = take(B * at.heads * T * 4);
+    L.attn_n = take(B * T * at.C * es);
   }
   L.train_total = off;
   return L;
@@ -882,6 +944,23 @@ extern "C" int cwdm_unet_create(const cwdm_unet_config* cfg, cwdm_unet** plan) {
   }
   CWDM_REQUIRE(!(cfg->additive_skips && cfg->use_freq), CWDM_E_UNSUPPORTED,
                "cwdm_unet_create: additive_skips with use_freq (WavUNetModel has no concatenation to replace)");
+  if (cfg->bottleneck_attention) {
+    CWDM_REQUIRE(!cfg->use_freq, CWDM_E_UNSUPPORTED,
+                 "cwdm_unet_create: bottleneck_attention with use_freq (WavUNetModel's middle block is not covered)");
+    const int C = cfg->channel_mult[cfg->num_levels - 1] * cfg->model_channels;
+    const int heads = cfg->num_head_channels > 0 ? C / cfg->num_head_channels : std::max(cfg->num_heads, 1);
+    CWDM_REQUIRE(heads >= 1 && C % heads == 0 && (cfg->num_head_channels <= 0 || C % cfg->num_head_channels == 0),
+                 CWDM_E_UNSUPPORTED,
+                 "cwdm_unet_create: bottleneck attention: " + std::to_string(C) + " channels not divisible into heads");
+    const int ch = C / heads;
+    CWDM_REQUIRE(ch % 16 == 0, CWDM_E_UNSUPPORTED,
+                 "cwdm_unet_create: bottleneck attention: head channels must be a multiple of 16, got " +
+                     std::to_string(ch));
+    CWDM_REQUIRE(ch <= 256, CWDM_E_UNSUPPORTED,
+                 "cwdm_unet_create: bottleneck attention: at most 256 head channels, got " + std::to_string(ch));
+    CWDM_REQUIRE(C / cfg->num_groups <= 256, CWDM_E_UNSUPPORTED,
+                 "cwdm_unet_create: bottleneck attention: at most 256 channels per GroupNorm group");
+  }
   if (cfg->use_freq) {
     // WavUNetModel as script_util.create_model builds it (:268-292)
     CWDM_REQUIRE(cfg->resblock_updown, CWDM_E_UNSUPPORTED,
@@ -1037,6 +1116,19 @@ extern "C" int cwdm_unet_pack(const cwdm_unet* uc, const float* const* P, void* 
     cp(g.gamma_p, g.gamma_off);
     cp(g.beta_p, g.beta_off);
   }
+  // the attention block's projections: row-major in the plan dtype, the qkv rows (and bias) permuted to
+  // [Q | K | V] when the model keeps the legacy per-head order
+  for (const auto& at : u->attns) {
+    const int legacy = u->cfg.attn_new_order ? 0 : 1;
+    if ((rc = cwdm::attn_pack(P[at.qkv_w_p], 3 * at.C, at.C, at.heads, at.ch, legacy, 0, u->cfg.dtype,
+                              base + at.qkv_w_off, s)))
+      return rc;
+    if ((rc = cwdm::attn_pack(P[at.qkv_b_p], 3 * at.C, 1, at.heads, at.ch, legacy, 0, CWDM_F32, base + at.qkv_b_off, s)))
+      return rc;
+    if ((rc = cwdm::attn_pack(P[at.proj_w_p], at.C, at.C, at.heads, at.ch, 0, 0, u->cfg.dtype, base + at.proj_w_off, s)))
+      return rc;
+    cp(at.proj_b_p, at.proj_b_off);
+  }
   if ((rc = copy_batch_run(u, cj, s))) return rc;
   if ((rc = ensure_table(u->pack_tab, u->pack_cap, jobs.size()))) return rc;
   return cwdm::pack_batch_run(jobs, u->cfg.dtype, u->pack_tab, u->pack_cache, s);
@@ -1059,6 +1151,10 @@ extern "C" double cwdm_unet_flops(const cwdm_unet* u, int64_t B, int64_t D, int6
   for (const auto& cs : u->convs) {
     const double v = (double)B * (D >> cs.level) * (H >> cs.level) * (W >> cs.level);
     f += 2.0 * v * cs.cout * (27.0 * (cs.s2 ? cs.cin_a / 8 : cs.cin_a) + cs.cin_b);  // algorithmic (stride-2: 27 C taps)
+  }
+  for (const auto& at : u->attns) {   // the qkv and proj GEMMs, q k^T and P v
+    const double T = (double)(D >> at.level) * (H >> at.level) * (W >> at.level);
+    f += 2.0 * B * T * at.C * (4.0 * at.C + 2.0 * T);
   }
   return f;
 }
@@ -1181,6 +1277,29 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
       if ((rc = cwdm_skip_avg(tptr(as.a), tptr(as.b), wb + L.t_off[as.out],
                               reinterpret_cast<float*>(wb + L.s_off[as.out]), u->cfg.dtype, B,
                               (D >> lv) * (H >> lv) * (W >> lv), as.channels, stream)))
+        return rc;
+      continue;
+    }
+    if (st.kind == kAttn) {
+      // (the norm's finalize ran just above: no conv takes it)
+      const auto& at = u->attns[st.idx];
+      const int64_t T = (D >> at.level) * (H >> at.level) * (W >> at.level);
+      const int dt = u->cfg.dtype, es = esize(dt), C = at.C;
+      unsigned char* qkv = wb + L.attn_qkv;
+      void* a = wb + L.attn_a;
+      if ((rc = cwdm::attn_linear(dt, B, T, C, 3 * C, tptr(at.src), reinterpret_cast<const float*>(wb + L.ss_off[at.gn]),
+                                  pk + at.qkv_w_off, P(at.qkv_b_off), nullptr, qkv, keep ? wb + L.attn_n : nullptr,
+                                  nullptr, s)))
+        return rc;
+      cwdm_attention_desc ad{};
+      ad.dtype = dt; ad.B = B; ad.T = T; ad.heads = at.heads; ad.ch = at.ch;
+      ad.q = qkv; ad.k = qkv + (int64_t)C * es; ad.v = qkv + (int64_t)2 * C * es;
+      ad.q_rs = ad.k_rs = ad.v_rs = 3 * C; ad.q_bs = ad.k_bs = ad.v_bs = T * 3 * C;
+      ad.o = a; ad.o_rs = C; ad.o_bs = T * C;
+      ad.L = keep ? reinterpret_cast<float*>(wb + L.attn_L) : nullptr;
+      if ((rc = cwdm_attention_forward(&ad, stream))) return rc;
+      if ((rc = cwdm::attn_linear(dt, B, T, C, C, a, nullptr, pk + at.proj_w_off, P(at.proj_b_off), tptr(at.src),
+                                  wb + L.t_off[at.out], nullptr, reinterpret_cast<float*>(wb + L.s_off[at.out]), s)))
         return rc;
       continue;
     }
@@ -1407,6 +1526,10 @@ struct GLayout {
   std::vector<int64_t> g_off;
   int64_t sync, tmp, dout, deb, dsil, gnws, gnws_bytes, split, split_bytes, wgws, wgws_bytes, dwe, chs, chs_bytes;
   int64_t gbp, gbp_bytes;   // fused GroupNorm-backward partials ([B][tiles][C][2]) + their slice sums
+  // the attention block: d qkv (B, T, 3 C), d a and d n (B, T, C), D (fp32 [B][heads][T]), the GroupNorm
+  // backward's per-(batch, channel) sums, and the packed-order qkv weight / bias gradient before its rows
+  // go back to the legacy order
+  int64_t at_dqkv = -1, at_da = -1, at_dn = -1, at_D = -1, at_part = -1, at_dw = -1;
   int64_t total;
 };
 
@@ -1448,6 +1571,7 @@ GLayout glayout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) 
     wgws = std::max(wgws, cwdm_conv3d_wgrad_workspace_bytes(cs.cout, cs.cin_a, 3));
     if (cs.ws_p >= 0) wgws = std::max(wgws, cwdm_conv3d_wgrad_workspace_bytes(cs.cout, cs.cin_b, 1));
   }
+  for (const auto& at : u->attns) wgws = std::max(wgws, cwdm_conv3d_wgrad_workspace_bytes(3 * at.C, at.C, 1));
   for (size_t i = 1; i < u->convs.size(); ++i) {
     const auto& cs = u->convs[i];
     const int64_t v = B * (D >> cs.level) * (H >> cs.level) * (W >> cs.level);
@@ -1477,8 +1601,20 @@ GLayout glayout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) 
   for (const auto& cs : u->convs)
     chs = std::max(chs, cwdm_channel_sum_workspace_bytes(B, (D >> cs.level) * (H >> cs.level) * (W >> cs.level),
                                                          std::max(cs.cout, 8)));
+  for (const auto& at : u->attns)
+    chs = std::max(chs, cwdm_channel_sum_workspace_bytes(B, (D >> at.level) * (H >> at.level) * (W >> at.level),
+                                                         3 * at.C));
   G.chs_bytes = chs;
   G.chs = take(chs);
+  for (const auto& at : u->attns) {
+    const int64_t T = (D >> at.level) * (H >> at.level) * (W >> at.level);
+    G.at_dqkv = take(B * T * 3 * at.C * es);
+    G.at_da = take(B * T * at.C * es);
+    G.at_dn = take(B * T * at.C * es);
+    G.at_D = take(B * at.heads * T * 4);
+    G.at_part = take(B * (int64_t)at.C * 2 * 4);
+    G.at_dw = take(((int64_t)3 * at.C * at.C + 3 * at.C) * 4);
+  }
   // the dgrad epilogue's GroupNorm-backward partials: one row per 32x4x4 tile
   // of the DMA conv (cwdm::GbwdFuse), then kGbSlices slice sums of them
   int64_t gbp = 0;
@@ -1517,6 +1653,14 @@ extern "C" int cwdm_unet_pack_bwd(const cwdm_unet* uc, const float* const* P, vo
         return rc;
       jobs.push_back(j);
     }
+  }
+  for (const auto& at : u->attns) {   // W^T of the two projections: their input gradients are row-major GEMMs too
+    if ((rc = cwdm::attn_pack(P[at.qkv_w_p], 3 * at.C, at.C, at.heads, at.ch, u->cfg.attn_new_order ? 0 : 1, 1,
+                              u->cfg.dtype, base + at.qkvT_off, (hipStream_t)stream)))
+      return rc;
+    if ((rc = cwdm::attn_pack(P[at.proj_w_p], at.C, at.C, at.heads, at.ch, 0, 1, u->cfg.dtype, base + at.projT_off,
+                              (hipStream_t)stream)))
+      return rc;
   }
   if ((rc = ensure_table(u->bwd_tab, u->bwd_cap, jobs.size()))) return rc;
   return cwdm::pack_batch_run(jobs, u->cfg.dtype, u->bwd_tab, u->bwd_cache, (hipStream_t)stream);
@@ -1709,6 +1853,63 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
       Pre pre;
       if ((rc = dgrad_gn(u->head_c, d16, u->head_g, hg.src0, -1, pre))) return rc;
       if ((rc = gn_bwd(u->head_g, hg.src0, -1, 0, &pre))) return rc;
+      continue;
+    }
+    if (seg <= nb && u->blocks[nb - seg].updown == 8) {
+      // the bottleneck AttentionBlock: y = x + proj_out(attention(qkv(GroupNorm(x))))
+      const Block& bk = u->blocks[nb - seg];
+      const auto& at = u->attns[bk.pool];
+      const auto& g = u->gns[at.gn];
+      CWDM_REQUIRE(kept, CWDM_E_WORKSPACE,
+                   "cwdm_unet_backward: the attention block needs the forward's training workspace "
+                   "(cwdm_unet_train_workspace_bytes: it keeps the log-sum-exp rows and the normalised input)");
+      const int C = at.C, lv = at.level, o = at.out, xt = at.src;
+      const int64_t T = vox(lv);
+      const unsigned char* qkv = wb + L.attn_qkv;
+      unsigned char* dqkv = gb + G.at_dqkv;
+      void* da = gb + G.at_da;
+      void* dn = gb + G.at_dn;
+      // ---- proj_out: bias, weight, input gradient
+      if ((rc = cwdm_channel_sum(grd(o), dt, B, T, C, C, nullptr, 0, GR(at.proj_b_p), nullptr, gb + G.chs, G.chs_bytes,
+                                 stream)))
+        return rc;
+      if ((rc = wgrad(lv, 1, wb + L.attn_a, C, nullptr, 0, 0, nullptr, grd(o), C, C, GR(at.proj_w_p)))) return rc;
+      if ((rc = cwdm::attn_linear(dt, B, T, C, C, grd(o), nullptr, pb + at.projT_off, nullptr, nullptr, da, nullptr,
+                                  nullptr, s)))
+        return rc;
+      // ---- softmax(q k^T) v
+      cwdm_attention_desc ad{};
+      ad.dtype = dt; ad.B = B; ad.T = T; ad.heads = at.heads; ad.ch = at.ch;
+      ad.q = qkv; ad.k = qkv + (int64_t)C * es; ad.v = qkv + (int64_t)2 * C * es;
+      ad.q_rs = ad.k_rs = ad.v_rs = 3 * C; ad.q_bs = ad.k_bs = ad.v_bs = T * 3 * C;
+      ad.o = const_cast<unsigned char*>(wb + L.attn_a); ad.o_rs = C; ad.o_bs = T * C;
+      ad.L = const_cast<float*>(reinterpret_cast<const float*>(wb + L.attn_L));
+      ad.D = reinterpret_cast<float*>(gb + G.at_D);
+      ad.d_o = da; ad.do_rs = C; ad.do_bs = T * C;
+      ad.dq = dqkv; ad.dk = dqkv + (int64_t)C * es; ad.dv = dqkv + (int64_t)2 * C * es;
+      ad.dq_rs = ad.dk_rs = ad.dv_rs = 3 * C; ad.dq_bs = ad.dk_bs = ad.dv_bs = T * 3 * C;
+      if ((rc = cwdm_attention_backward(&ad, stream))) return rc;
+      // ---- qkv: bias, weight (rows back to the model's order), input gradient
+      const bool legacy = !u->cfg.attn_new_order;
+      float* dwp = legacy ? reinterpret_cast<float*>(gb + G.at_dw) : GR(at.qkv_w_p);
+      float* dbp = legacy ? dwp + (int64_t)3 * C * C : GR(at.qkv_b_p);
+      if (legacy) CWDM_HIP(hipMemsetAsync(dwp, 0, ((int64_t)3 * C * C + 3 * C) * 4, s));
+      if ((rc = cwdm_channel_sum(dqkv, dt, B, T, 3 * C, 3 * C, nullptr, 0, dbp, nullptr, gb + G.chs, G.chs_bytes,
+                                 stream)))
+        return rc;
+      if ((rc = wgrad(lv, 1, wb + L.attn_n, C, nullptr, 0, 0, nullptr, dqkv, 3 * C, 3 * C, dwp))) return rc;
+      if (legacy) {
+        if ((rc = cwdm::attn_unperm_add(dwp, GR(at.qkv_w_p), 3 * C, C, at.heads, at.ch, s))) return rc;
+        if ((rc = cwdm::attn_unperm_add(dbp, GR(at.qkv_b_p), 3 * C, 1, at.heads, at.ch, s))) return rc;
+      }
+      if ((rc = cwdm::attn_linear(dt, B, T, 3 * C, C, dqkv, nullptr, pb + at.qkvT_off, nullptr, nullptr, dn, nullptr,
+                                  nullptr, s)))
+        return rc;
+      // ---- the norm (no activation) and the residual: dx = dy + dGN(dn)
+      if ((rc = cwdm::gn_lin_bwd(dt, B, T, C, u->cfg.num_groups, act(xt), dn, mr_of(at.gn), P(g.gamma_off), grd(o),
+                                 grd(xt), take_acc(xt), reinterpret_cast<float*>(gb + G.at_part), GR(g.gamma_p),
+                                 GR(g.beta_p), s)))
+        return rc;
       continue;
     }
     if (seg <= nb && u->blocks[nb - seg].updown == 7) {

@@ -94,6 +94,36 @@ class UNetConfig(ctypes.Structure):
         ("num_groups", ctypes.c_int), ("dtype", ctypes.c_int),
         ("resblock_updown", ctypes.c_int), ("use_freq", ctypes.c_int),
         ("mfma_split", ctypes.c_int), ("additive_skips", ctypes.c_int),
+        ("bottleneck_attention", ctypes.c_int), ("num_heads", ctypes.c_int),
+        ("num_head_channels", ctypes.c_int), ("attn_new_order", ctypes.c_int),
+    ]
+
+
+class AttentionDesc(ctypes.Structure):
+    _fields_ = [
+        ("dtype", ctypes.c_int),
+        ("B", i64), ("T", i64),
+        ("heads", ctypes.c_int), ("ch", ctypes.c_int),
+        ("q", vp), ("k", vp), ("v", vp),
+        ("q_rs", i64), ("k_rs", i64), ("v_rs", i64),
+        ("q_bs", i64), ("k_bs", i64), ("v_bs", i64),
+        ("o", vp), ("o_rs", i64), ("o_bs", i64),
+        ("L", vp),
+        ("D", vp),
+        ("d_o", vp), ("do_rs", i64), ("do_bs", i64),
+        ("dq", vp), ("dk", vp), ("dv", vp),
+        ("dq_rs", i64), ("dk_rs", i64), ("dv_rs", i64),
+        ("dq_bs", i64), ("dk_bs", i64), ("dv_bs", i64),
+    ]
+
+
+class AttnLinearDesc(ctypes.Structure):
+    _fields_ = [
+        ("dtype", ctypes.c_int),
+        ("B", i64), ("T", i64),
+        ("K", ctypes.c_int), ("N", ctypes.c_int),
+        ("in_", vp), ("gn", vp), ("w", vp), ("bias", vp), ("res", vp),
+        ("out", vp), ("n_out", vp), ("stats", vp),
     ]
 
 
@@ -194,6 +224,12 @@ _PROTOS = {
     "cwdm_skip_avg": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, i64, i64, ctypes.c_int, vp]),
     "cwdm_skip_avg_bwd": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, i64, i64,
                                          ctypes.c_int, vp]),
+    "cwdm_attention_forward": (ctypes.c_int, [ctypes.POINTER(AttentionDesc), vp]),
+    "cwdm_attention_backward": (ctypes.c_int, [ctypes.POINTER(AttentionDesc), vp]),
+    "cwdm_attn_parts": (i64, [i64]),
+    "cwdm_attn_linear": (ctypes.c_int, [ctypes.POINTER(AttnLinearDesc), vp]),
+    "cwdm_attn_pack": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_int, vp, vp]),
     "cwdm_wavelet2_analysis": (ctypes.c_int, [vp, i64, i64, i64, i64, vp, ctypes.c_int, i64, i64, ctypes.c_int, vp]),
     "cwdm_wavelet2_synthesis": (ctypes.c_int, [vp, i64, i64, i64, i64, i64, i64, ctypes.c_int, vp, vp]),
     "cwdm_unet_param_info": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(i64),

@@ -10,13 +10,19 @@ compute dtype (``compute_dtype`` = "fp32" for reference numerics, "bf16" or
 "fp16" for throughput -- the same MFMA rate on gfx950, fp16 with 3 more mantissa
 bits); parameters stay fp32 masters and are re-packed when they change.
 
-Supported configuration family: the one run.sh uses (dims=3, no attention,
-use_scale_shift_norm=False, resample_2d=False), with the skips concatenated or,
-with additive_skips=True, averaged into the decoder (h = (h + skip) / 2 as one
-``cwdm_skip_avg`` pass per output block; run.sh's memory-saving switch), and
-either resblock_updown=True (run.sh: ResBlock down/up) or resblock_updown=False
-with conv_resample=True (Downsample = stride-2 Conv3d, Upsample = nearest x2 +
-Conv3d; unet.py:40-100).  Anything else raises NotImplementedError.
+Supported configuration family: the one run.sh uses (dims=3, no per-level
+attention, use_scale_shift_norm=False, resample_2d=False), with the skips
+concatenated or, with additive_skips=True, averaged into the decoder
+(h = (h + skip) / 2 as one ``cwdm_skip_avg`` pass per output block; run.sh's
+memory-saving switch), either resblock_updown=True (run.sh: ResBlock down/up) or
+resblock_updown=False with conv_resample=True (Downsample = stride-2 Conv3d,
+Upsample = nearest x2 + Conv3d; unet.py:40-100), and with or without the middle
+block's AttentionBlock (bottleneck_attention, the constructor default; num_heads,
+num_head_channels, use_new_attention_order as in the reference; head channels a
+multiple of 16, at most 256): GroupNorm + qkv projection, a streaming MFMA
+softmax(QK^T)V and proj_out + residual, three launches.
+``attention_resolutions`` must stay empty.  Anything else raises
+NotImplementedError.
 """
 import math
 import os
@@ -77,8 +83,6 @@ class UNetModel(nn.Module):
             unsupported.append(f"dims={dims} (3D only)")
         if attention_resolutions:
             unsupported.append("attention blocks")
-        if bottleneck_attention:
-            unsupported.append("bottleneck_attention=True")
         if not resblock_updown and not conv_resample:
             unsupported.append("resblock_updown=False with conv_resample=False (parameter-free pool / nearest layers)")
         if use_scale_shift_norm:
@@ -95,14 +99,15 @@ class UNetModel(nn.Module):
         self._setup_native(image_size, in_channels, model_channels, out_channels, num_res_blocks,
                            attention_resolutions, dropout, channel_mult, conv_resample, num_classes, use_checkpoint,
                            num_heads, num_groups, resblock_updown, bottleneck_attention, additive_skips,
-                           decoder_device_thresh, compute_dtype)
+                           decoder_device_thresh, compute_dtype, num_head_channels=num_head_channels,
+                           use_new_attention_order=use_new_attention_order)
 
     use_freq = False
 
     def _setup_native(self, image_size, in_channels, model_channels, out_channels, num_res_blocks,
                       attention_resolutions, dropout, channel_mult, conv_resample, num_classes, use_checkpoint,
                       num_heads, num_groups, resblock_updown, bottleneck_attention, additive_skips,
-                      decoder_device_thresh, compute_dtype):
+                      decoder_device_thresh, compute_dtype, num_head_channels=-1, use_new_attention_order=False):
         self.image_size = image_size
         self.in_channels = in_channels
         self.model_channels = model_channels
@@ -115,6 +120,8 @@ class UNetModel(nn.Module):
         self.num_classes = num_classes
         self.use_checkpoint = use_checkpoint
         self.num_heads = num_heads
+        self.num_head_channels = num_head_channels
+        self.use_new_attention_order = bool(use_new_attention_order)
         self.num_groups = num_groups
         self.resblock_updown = bool(resblock_updown)
         self.bottleneck_attention = bottleneck_attention
@@ -214,13 +221,15 @@ class UNetModel(nn.Module):
     # ---- parameters -------------------------------------------------------
     def _reset_parameters(self):
         """PyTorch default init of Conv3d/Linear/GroupNorm plus the reference's
-        zero_module on out_layers.3 and out.2 (unet.py:259-261, :724)."""
+        zero_module on out_layers.3, out.2 (unet.py:259-261, :724) and the attention
+        block's proj_out (:340)."""
         with th.no_grad():
             for name, p in self.named_parameters():
                 if name.endswith("out_layers.3.weight") or name.endswith("out_layers.3.bias") or \
-                        name.startswith("out.2."):
+                        name.startswith("out.2.") or name.startswith("middle_block.1.proj_out."):
                     p.zero_()
-                elif p.dim() == 1 and (".in_layers.0." in name or ".out_layers.0." in name or name.startswith("out.0.")):
+                elif p.dim() == 1 and (".in_layers.0." in name or ".out_layers.0." in name or
+                                       name.startswith("out.0.") or name.startswith("middle_block.1.norm.")):
                     p.fill_(1.0 if name.endswith("weight") else 0.0)
                 elif p.dim() >= 2:
                     fan_in = p[0].numel()
@@ -238,7 +247,10 @@ class UNetModel(nn.Module):
             self._plans[key] = UNetPlan(self.in_channels, self.model_channels, self.out_channels,
                                         self.num_res_blocks, self.channel_mult, self.num_groups, dtype,
                                         resblock_updown=self.resblock_updown, use_freq=self.use_freq,
-                                        additive_skips=bool(self.additive_skips))
+                                        additive_skips=bool(self.additive_skips),
+                                        bottleneck_attention=bool(self.bottleneck_attention),
+                                        num_heads=self.num_heads, num_head_channels=self.num_head_channels,
+                                        use_new_attention_order=self.use_new_attention_order)
         return self._plans[key]
 
     @property
@@ -400,8 +412,9 @@ class _UNetTrain(th.autograd.Function):
         xin, t = model._prep_inputs(x, timesteps)
         # the training workspace: the forward keeps each DMA-staged conv's
         # activated input there for the backward's weight gradients
-        nbytes = plan.train_workspace_bytes(B, D, H, W) if model.keep_activations else \
-            plan.workspace_bytes(B, D, H, W)
+        # (the attention block's backward needs what only the training workspace keeps)
+        nbytes = plan.train_workspace_bytes(B, D, H, W) if model.keep_activations or model.bottleneck_attention \
+            else plan.workspace_bytes(B, D, H, W)
         ws = th.empty(nbytes, dtype=th.uint8, device=x.device)
         out_nd = th.empty((B, D, H, W, model.out_channels), dtype=th.float32, device=x.device)
         plan.forward(model.packed_weights(), xin, t, out_nd, B, D, H, W, ws=ws)

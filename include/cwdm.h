@@ -130,6 +130,75 @@ int cwdm_skip_avg(const void* a, const void* b, void* out, float* stats, int dty
 int cwdm_skip_avg_bwd(const void* dy, void* da, int acc_a, void* db, int acc_b, int dtype, int64_t B, int64_t V,
                       int C, cwdm_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Attention of UNetModel(bottleneck_attention=True): AttentionBlock with
+ * QKVAttention / QKVAttentionLegacy (guided_diffusion/unet.py:314-444) over the
+ * T = d h w voxels of the coarsest grid (fast-cwdm_amd/csrc/attention.hip).
+ *
+ * cwdm_attention_forward: o[b, t, h ch + c] = sum_s softmax_s(q_t . k_s / sqrt(ch)) v_s[c]
+ *   per batch b and head h.  q, k, v, o: dtype (CWDM_F32 / CWDM_BF16 / CWDM_F16),
+ *   element (b, t, head h, channel c) of X at X + b X_bs + t X_rs + h ch + c
+ *   (strides in elements; rows and, for B > 1, batches 16-byte aligned; an
+ *   input's batch stride may be 0, an output's must cover its batch's rows:
+ *   CWDM_E_SHAPE otherwise) -- e.g. three column ranges of one
+ *   (B, T, 3 heads ch) projection.  Streaming softmax: fp32 scores scaled in
+ *   fp32, fp32 running max / sum, P rounded to dtype only as the MFMA operand of
+ *   P V; any T >= 1 (keys past T masked, rows past T not stored), ch a multiple
+ *   of 16 in [16, 256].  L: NULL or fp32 [B][heads][T], the log-sum-exp of each
+ *   row's scaled scores (the backward needs it).
+ * cwdm_attention_backward: dq, dk, dv (dtype, addressed like q) from d_o, the
+ *   forward's q, k, v, o, L and D, fp32 scratch [B][heads][T] (D_t = d_o_t . o_t).
+ *   One kernel per key tile (dk, dv) and one per query tile (dq) recompute P
+ *   from q, k and L: no atomics, two calls give the same bits.
+ * A shape outside these rules returns CWDM_E_UNSUPPORTED.
+ *
+ * cwdm_attn_linear: the block's 1x1 projections as one row-major GEMM,
+ *   out[b, t, n] = sum_c in'[b, t, c] w[n][c] (+ bias[n]) (+ res[b, t, n]);
+ *   in' = in, or with gn ([B][K][2] fp32 scale / shift of cwdm_gn_finalize)
+ *   in * scale + shift rounded to dtype: GroupNorm WITHOUT an activation (the
+ *   block's norm, unet.py:335) fused into the qkv projection.  in (B, T, K),
+ *   out / res (B, T, N) contiguous in dtype, w [N][K] in dtype
+ *   (cwdm_attn_pack), bias fp32; K, N multiples of 16.  n_out (optional): in'
+ *   (B, T, K), kept for the projection's weight gradient.  stats (optional):
+ *   fp32 [B][cwdm_attn_parts(T)][N][2] (sum, sum^2) of the fp32 result before
+ *   rounding, one row per 16-row tile in a fixed order (proj_out's output feeds
+ *   the next ResBlock's GroupNorm).
+ * cwdm_attn_pack: fp32 [rows][cols] -> dtype [rows][cols] (transpose 0) or
+ *   [cols][rows] (transpose 1, the input-gradient form).  legacy != 0
+ *   (rows = 3 heads ch): packed row s C + i ch + j (s = q, k, v; C = heads ch)
+ *   comes from source row i 3 ch + s ch + j, the row order of
+ *   QKVAttentionLegacy; the kernels see [Q | K | V] only.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  int dtype;
+  int64_t B, T;
+  int heads, ch;
+  const void* q; const void* k; const void* v;
+  int64_t q_rs, k_rs, v_rs;   /* row strides */
+  int64_t q_bs, k_bs, v_bs;   /* batch strides */
+  void* o; int64_t o_rs, o_bs;
+  float* L;
+  /* backward only */
+  float* D;
+  const void* d_o; int64_t do_rs, do_bs;
+  void* dq; void* dk; void* dv;
+  int64_t dq_rs, dk_rs, dv_rs;
+  int64_t dq_bs, dk_bs, dv_bs;
+} cwdm_attention_desc;
+int cwdm_attention_forward(const cwdm_attention_desc* desc, cwdm_stream_t stream);
+int cwdm_attention_backward(const cwdm_attention_desc* desc, cwdm_stream_t stream);
+typedef struct {
+  int dtype;
+  int64_t B, T;
+  int K, N;
+  const void* in; const float* gn; const void* w; const float* bias; const void* res;
+  void* out; void* n_out; float* stats;
+} cwdm_attn_linear_desc;
+int64_t cwdm_attn_parts(int64_t T);
+int cwdm_attn_linear(const cwdm_attn_linear_desc* desc, cwdm_stream_t stream);
+int cwdm_attn_pack(const float* w, int rows, int cols, int heads, int ch, int legacy, int transpose, int dtype,
+                   void* out, cwdm_stream_t stream);
+
 /* cwdm_prepare_batch: the i2i front end of training_losses
  * (guided_diffusion/gaussian_diffusion.py:1131-1149) in one pass -- Haar DWT of
  * the target and the three condition volumes (LLL / 3), of the noise image (no
@@ -590,9 +659,11 @@ int cwdm_adamw_device_step(float* p, const float* g, float* m, float* v, int64_t
 
 /* ---------------------------------------------------------------------------
  * U-Net plan: the whole UNetModel.forward (guided_diffusion/unet.py:754-800)
- * for the run.sh configuration family (no attention, resblock_updown=True,
+ * for the run.sh configuration family (resblock_updown=True,
  * use_scale_shift_norm=False, resample_2d=False, dims=3; skips concatenated or,
- * with additive_skips, averaged: cwdm_skip_avg).
+ * with additive_skips, averaged: cwdm_skip_avg; no per-level attention, and
+ * with bottleneck_attention the middle block's AttentionBlock:
+ * cwdm_attention_forward between cwdm_attn_linear's two projections).
  * Topology and parameter names/shapes follow UNetModel.__init__
  * (unet.py:482-725) so reference state_dicts load unchanged.
  * ------------------------------------------------------------------------- */
@@ -613,6 +684,13 @@ typedef struct {
   int additive_skips;  /* 1: every output block takes h = (h + skip) / 2 instead of cat([h, skip])
                           (unet.py:661-719, :793-794); its first ResBlock maps ch -> the next skip's channels.
                           Not with use_freq */
+  int bottleneck_attention; /* 1: an AttentionBlock between the two middle ResBlocks (unet.py:635-642): parameters
+                               middle_block.1.{norm,qkv,proj_out}.*, the second ResBlock becomes middle_block.2.
+                               Not with use_freq; head channels a multiple of 16, <= 256.  0 (and a zeroed
+                               struct): no attention */
+  int num_heads;            /* heads of that block when num_head_channels <= 0 (0 reads as 1) */
+  int num_head_channels;    /* > 0: heads = channels / num_head_channels */
+  int attn_new_order;       /* use_new_attention_order: qkv rows [Q | K | V] instead of per head [q | k | v] */
 } cwdm_unet_config;
 
 int cwdm_unet_create(const cwdm_unet_config* cfg, cwdm_unet** plan);
@@ -636,7 +714,9 @@ int64_t cwdm_unet_workspace_bytes(const cwdm_unet* plan, int64_t B, int64_t D, i
  * writes one (16-bit plans, DMA-staged levels).  A forward given at least this
  * many bytes keeps them there, and cwdm_unet_backward on that workspace stages
  * those convs' weight gradients from them by LDS-DMA instead of recomputing the
- * GroupNorm+SiLU (cwdm_wgrad_desc.u_cm). */
+ * GroupNorm+SiLU (cwdm_wgrad_desc.u_cm).  With bottleneck_attention it also
+ * holds the attention rows' log-sum-exp and the block's normalised input, which
+ * cwdm_unet_backward needs: on a smaller workspace it returns CWDM_E_WORKSPACE. */
 int64_t cwdm_unet_train_workspace_bytes(const cwdm_unet* plan, int64_t B, int64_t D, int64_t H, int64_t W);
 /* x: NDHWC (B, D, H, W, in_channels) in plan dtype; t: device fp32[B] model timesteps;
  * out: NDHWC fp32 (B, D, H, W, out_channels). */
