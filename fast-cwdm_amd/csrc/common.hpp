@@ -220,5 +220,17 @@ struct GnFinFuse {
   float* mr;   // [B][groups][2]
   long long B;
   bool used;
+  // FiLM (use_scale_shift_norm): the embedding rows [s | t] of batch entry b at film + b * film_bs,
+  // folded into (scale, shift) by the finalize (film_fold); null: a plain GroupNorm
+  const float* film;
+  long long film_bs;
 };
+
+// FiLM folded into a GroupNorm's (scale, shift) pair: (x sc + sh)(1 + s) + t = x sc' + sh'.
+// The one rounding sequence of both finalize sites (norm.hip, conv3d_v4.hip).
+__device__ __forceinline__ void film_fold(float& sc, float& sh, float s, float t) {
+  const float e = 1.0f + s;
+  sc = sc * e;
+  sh = __fmaf_rn(sh, e, t);
+}
 }  // namespace cwdm

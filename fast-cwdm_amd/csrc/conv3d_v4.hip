@@ -115,10 +115,17 @@ struct GnFinApplyArgs {
   const float* gamma; const float* beta; int groups; double n; float eps;
   float* ss; float* mr; void* out;
   int V, vblk;   // voxels per batch entry, voxels per workgroup
+  static constexpr bool kFilm = false;
+};
+// ... of a FiLM ResBlock's out_layers.0: the rows [s | t] folded into the pair (film_fold), as
+// gn_finalize_film_kernel does.  Its own instantiation: the plain kernel's arguments and code stay as they are.
+struct GnFinApplyFilmArgs : GnFinApplyArgs {
+  const float* film; long long film_bs;
+  static constexpr bool kFilm = true;
 };
 
-template <typename T>
-__global__ void __launch_bounds__(256) gn_fin_apply_kernel(GnFinApplyArgs a) {
+template <typename T, typename Args = GnFinApplyArgs>
+__global__ void __launch_bounds__(256) gn_fin_apply_kernel(Args a) {
   const int j = blockIdx.x, vb = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
   const int C = a.c0 + a.c1, cpg = C / a.groups, c16 = 16 * j;
   const bool first = c16 < a.c0;
@@ -156,8 +163,9 @@ __global__ void __launch_bounds__(256) gn_fin_apply_kernel(GnFinApplyArgs a) {
     const float rstd = (float)(1.0 / sqrt(var + (double)a.eps));
     const float meanf = (float)mean;
     const int c = c16 + t;
-    const float sc = a.gamma[c] * rstd;
-    const float sh = a.beta[c] - meanf * sc;
+    float sc = a.gamma[c] * rstd;
+    float sh = a.beta[c] - meanf * sc;
+    if constexpr (Args::kFilm) film_fold(sc, sh, a.film[b * a.film_bs + c], a.film[b * a.film_bs + C + c]);
     tab[2 * t] = sc;
     tab[2 * t + 1] = sh;
     if (vb == 0) {
@@ -209,6 +217,9 @@ int cu_count() {
 int gnfin_flush(const cwdm_conv3d_desc* d, GnFinFuse* f, hipStream_t s) {
   if (!f || f->used || !d->a_gn || f->ss != d->a_gn) return CWDM_OK;
   f->used = true;
+  if (f->film)
+    return cwdm_gn_finalize_film(f->s0, f->p0, f->c0, f->s1, f->p1, f->c1, f->gamma, f->beta, f->groups, f->B,
+                                 f->voxels, f->eps, f->ss, f->mr, f->film, f->film_bs, s);
   return cwdm_gn_finalize(f->s0, f->p0, f->c0, f->s1, f->p1, f->c1, f->gamma, f->beta, f->groups, f->B, f->voxels,
                           f->eps, f->ss, f->mr, s);
 }
@@ -230,7 +241,7 @@ bool gn_fin_fusable(const GnFinFuse& f, int dtype, int c0, int c1) {
 namespace {
 int gn_fin_apply(const GnFinFuse& f, const void* x0, int c0, const void* x1, int c1, int64_t B, int64_t V, int dtype,
                  void* out, hipStream_t s) {
-  GnFinApplyArgs a{};
+  GnFinApplyFilmArgs a{};
   a.x0 = x0; a.c0 = c0; a.x1 = x1; a.c1 = c1;
   a.s0 = f.s0; a.p0 = f.p0; a.s1 = f.s1; a.p1 = f.p1;
   a.gamma = f.gamma; a.beta = f.beta; a.groups = f.groups;
@@ -245,8 +256,16 @@ int gn_fin_apply(const GnFinFuse& f, const void* x0, int c0, const void* x1, int
   nvb = ceil_div(V, (long long)a.vblk);
   CWDM_REQUIRE(B < 65536 && nvb < 65536, CWDM_E_UNSUPPORTED, "gn_fin_apply: grid too large");
   const dim3 grid((unsigned)nchunk, (unsigned)nvb, (unsigned)B);
-  if (dtype == CWDM_F16) hipLaunchKernelGGL(gn_fin_apply_kernel<f16_t>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(gn_fin_apply_kernel<bf16_t>, grid, dim3(256), 0, s, a);
+  if (f.film) {
+    a.film = f.film; a.film_bs = f.film_bs;
+    if (dtype == CWDM_F16) hipLaunchKernelGGL((gn_fin_apply_kernel<f16_t, GnFinApplyFilmArgs>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gn_fin_apply_kernel<bf16_t, GnFinApplyFilmArgs>), grid, dim3(256), 0, s, a);
+    CWDM_LAUNCHED();
+    return CWDM_OK;
+  }
+  const GnFinApplyArgs& pa = a;
+  if (dtype == CWDM_F16) hipLaunchKernelGGL(gn_fin_apply_kernel<f16_t>, grid, dim3(256), 0, s, pa);
+  else hipLaunchKernelGGL(gn_fin_apply_kernel<bf16_t>, grid, dim3(256), 0, s, pa);
   CWDM_LAUNCHED();
   return CWDM_OK;
 }
@@ -673,6 +692,32 @@ extern "C" int cwdm_debug_gn_fin_apply(const float* stats0, int64_t parts0, int 
   f.ss = scale_shift; f.mr = mean_rstd; f.B = B;
   CWDM_REQUIRE(gn_fin_fusable(f, dtype, c0, c1), CWDM_E_UNSUPPORTED,
                "cwdm_debug_gn_fin_apply: not a fusable shape (16-bit, 16-channel chunks, <= 16 channels per "
+               "group dividing 16, <= 256 partials)");
+  return gn_fin_apply(f, x0, c0, x1, c1, B, voxels, dtype, out_cm, (hipStream_t)stream);
+}
+
+// ... of a FiLM block's norm (GnFinFuse::film): compared with cwdm_gn_finalize_film + cwdm_gn_apply
+extern "C" int cwdm_debug_gn_fin_apply_film(const float* stats0, int64_t parts0, int c0, const float* stats1,
+                                            int64_t parts1, int c1, const float* gamma, const float* beta,
+                                            int groups, int64_t B, int64_t voxels, float eps, const void* x0,
+                                            const void* x1, int dtype, float* scale_shift, float* mean_rstd,
+                                            void* out_cm, const float* film, int64_t film_bstride,
+                                            cwdm_stream_t stream) {
+  CWDM_REQUIRE(stats0 && x0 && gamma && beta && scale_shift && mean_rstd && out_cm && film &&
+                   (c1 == 0 || (stats1 && x1)),
+               CWDM_E_INVALID, "cwdm_debug_gn_fin_apply_film: null pointer");
+  CWDM_REQUIRE(B > 0 && voxels > 0 && parts0 > 0 && (c1 == 0 || parts1 > 0), CWDM_E_SHAPE,
+               "cwdm_debug_gn_fin_apply_film: empty shape");
+  CWDM_REQUIRE(film_bstride >= 2 * (int64_t)(c0 + c1), CWDM_E_SHAPE,
+               "cwdm_debug_gn_fin_apply_film: film rows need a batch stride of at least 2 C");
+  GnFinFuse f{};
+  f.s0 = stats0; f.p0 = parts0; f.c0 = c0;
+  f.s1 = stats1; f.p1 = parts1; f.c1 = c1;
+  f.gamma = gamma; f.beta = beta; f.groups = groups; f.voxels = voxels; f.eps = eps;
+  f.ss = scale_shift; f.mr = mean_rstd; f.B = B;
+  f.film = film; f.film_bs = film_bstride;
+  CWDM_REQUIRE(gn_fin_fusable(f, dtype, c0, c1), CWDM_E_UNSUPPORTED,
+               "cwdm_debug_gn_fin_apply_film: not a fusable shape (16-bit, 16-channel chunks, <= 16 channels per "
                "group dividing 16, <= 256 partials)");
   return gn_fin_apply(f, x0, c0, x1, c1, B, voxels, dtype, out_cm, (hipStream_t)stream);
 }

@@ -167,12 +167,18 @@ __global__ void __launch_bounds__(256) gn_bwd_reduce_kernel(const T* __restrict_
 // each, fixed order), the group terms, the apply coefficients and dgamma /
 // dbeta.  (One workgroup for all channels ran 10 us per call, 71 calls per
 // training step.)
-__global__ void __launch_bounds__(256) gn_bwd_finalize_kernel(const float* __restrict__ part, int nblk, int C,
-                                                             int B, const float* __restrict__ gamma,
-                                                             const float* __restrict__ mr, int groups,
-                                                             long long V, float* __restrict__ coef,
-                                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                             int acc_affine) {
+// FILM (a FiLM ResBlock's out_layers.0, z = (gamma nhat + beta)(1 + s) + t with the rows [s | t] of
+// batch entry b at film + b * film_bs): e = 1 + s_bc scales gamma in the group terms and k1 and the
+// sums going into dgamma / dbeta; d s_bc = gamma_c cB + beta_c cA and d t_bc = cA are written to
+// dfilm + b * dfilm_bs + [c | C + c].
+template <bool FILM>
+__device__ __forceinline__ void gn_bwd_finalize_body(const float* __restrict__ part, int nblk, int C, int B,
+                                                     const float* __restrict__ gamma, const float* __restrict__ mr,
+                                                     int groups, long long V, float* __restrict__ coef,
+                                                     float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                     int acc_affine, const float* __restrict__ beta,
+                                                     const float* __restrict__ film, long long film_bs,
+                                                     float* __restrict__ dfilm, long long dfilm_bs) {
   __shared__ double rA[256], rB[256], cA[1024], cB[1024], dG[1024], dB[1024], gs[2];
   const int g = blockIdx.x, cpg = C / groups, c0 = g * cpg;
   const int t = threadIdx.x;
@@ -204,15 +210,25 @@ __global__ void __launch_bounds__(256) gn_bwd_finalize_kernel(const float* __res
         double sa = 0.0, sb = 0.0;
         for (int k = 0; k < sub; ++k) { sa += rA[k * cw + t]; sb += rB[k * cw + t]; }
         cA[w0 + t] = sa; cB[w0 + t] = sb;
-        dG[w0 + t] += sb; dB[w0 + t] += sa;
+        if constexpr (FILM) {
+          const int c = c0 + w0 + t;
+          const double e = (double)(1.0f + film[b * film_bs + c]);
+          dG[w0 + t] += e * sb; dB[w0 + t] += e * sa;
+          dfilm[b * dfilm_bs + c] = (float)((double)gamma[c] * sb + (double)beta[c] * sa);
+          dfilm[b * dfilm_bs + C + c] = (float)sa;
+        } else {
+          dG[w0 + t] += sb; dB[w0 + t] += sa;
+        }
       }
       __syncthreads();
     }
     if (t == 0) {
       double a = 0.0, bb = 0.0;
       for (int c = 0; c < cpg; ++c) {
-        a += (double)gamma[c0 + c] * cA[c];
-        bb += (double)gamma[c0 + c] * cB[c];
+        double ge = (double)gamma[c0 + c];
+        if constexpr (FILM) ge *= (double)(1.0f + film[b * film_bs + c0 + c]);
+        a += ge * cA[c];
+        bb += ge * cB[c];
       }
       gs[0] = a; gs[1] = bb;
     }
@@ -220,7 +236,8 @@ __global__ void __launch_bounds__(256) gn_bwd_finalize_kernel(const float* __res
     const double N = (double)cpg * (double)V;
     const double mu = mr[((long long)b * groups + g) * 2], rs = mr[((long long)b * groups + g) * 2 + 1];
     for (int c = t; c < cpg; c += 256) {
-      const double k1 = rs * gamma[c0 + c];
+      double k1 = rs * gamma[c0 + c];
+      if constexpr (FILM) k1 *= (double)(1.0f + film[b * film_bs + c0 + c]);
       const double k2 = -rs * rs * gs[1] / N;
       const double k3 = -rs * gs[0] / N + rs * rs * gs[1] * mu / N;
       coef[((long long)b * C + c0 + c) * 4 + 0] = (float)k1;
@@ -235,6 +252,25 @@ __global__ void __launch_bounds__(256) gn_bwd_finalize_kernel(const float* __res
     dgamma[cc] = acc_affine ? dgamma[cc] + (float)dG[c] : (float)dG[c];
     dbeta[cc] = acc_affine ? dbeta[cc] + (float)dB[c] : (float)dB[c];
   }
+}
+
+__global__ void __launch_bounds__(256) gn_bwd_finalize_kernel(const float* __restrict__ part, int nblk, int C,
+                                                             int B, const float* __restrict__ gamma,
+                                                             const float* __restrict__ mr, int groups,
+                                                             long long V, float* __restrict__ coef,
+                                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                             int acc_affine) {
+  gn_bwd_finalize_body<false>(part, nblk, C, B, gamma, mr, groups, V, coef, dgamma, dbeta, acc_affine, nullptr,
+                              nullptr, 0, nullptr, 0);
+}
+
+__global__ void __launch_bounds__(256) gn_bwd_finalize_film_kernel(
+    const float* __restrict__ part, int nblk, int C, int B, const float* __restrict__ gamma,
+    const float* __restrict__ mr, int groups, long long V, float* __restrict__ coef, float* __restrict__ dgamma,
+    float* __restrict__ dbeta, int acc_affine, const float* __restrict__ beta, const float* __restrict__ film,
+    long long film_bs, float* __restrict__ dfilm, long long dfilm_bs) {
+  gn_bwd_finalize_body<true>(part, nblk, C, B, gamma, mr, groups, V, coef, dgamma, dbeta, acc_affine, beta, film,
+                             film_bs, dfilm, dfilm_bs);
 }
 
 template <typename T> __device__ __forceinline__ float stored(float v) {
@@ -741,9 +777,14 @@ int cwdm::gn_silu_bwd_impl(const void* x0, int c0, const void* x1, int c1, const
                            int64_t h, int64_t w, int dtype, void* dx0, int acc0, void* dx1, int acc1, float* dgamma,
                            float* dbeta, void* ws, int64_t ws_bytes, float* chs, int64_t chs_stride,
                            cwdm_stream_t stream, int acc_affine, const float* pre_part, int pre_nblk,
-                           const float** coef_out) {
+                           const float** coef_out, const GnBwdFilm* film) {
   CWDM_REQUIRE(!chs || (c1 == 0 && chs_stride >= c0), CWDM_E_UNSUPPORTED,
                "gn_silu_bwd: fused channel sums need one source");
+  CWDM_REQUIRE(!film || (film->beta && film->film && film->dfilm && film->film_bs >= 2 * (c0 + c1) &&
+                         film->dfilm_bs >= 2 * (c0 + c1)),
+               CWDM_E_INVALID, "gn_silu_bwd: FiLM rows missing or their batch stride below 2 C");
+  CWDM_REQUIRE(!film || !film->chs_c || (!chs && c1 == 0), CWDM_E_UNSUPPORTED,
+               "gn_silu_bwd: per-channel sums need one source and no per-batch sums");
   CWDM_REQUIRE(x0 && du && ss && mr && gamma && dx0 && dgamma && dbeta && ws, CWDM_E_INVALID,
                "cwdm_gn_silu_bwd: null pointer");
   CWDM_REQUIRE(c1 == 0 || (x1 && dx1), CWDM_E_INVALID, "cwdm_gn_silu_bwd: second source missing");
@@ -784,13 +825,19 @@ int cwdm::gn_silu_bwd_impl(const void* x0, int c0, const void* x1, int c1, const
          return CWDM_OK;
        })))
     return rc;
-  hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3((unsigned)groups), dim3(256), 0, s, pre_part ? pre_part : part,
-                     pre_part ? pre_nblk : (int)nb, C, (int)B, gamma, mr, groups, V, coef, dgamma, dbeta, acc_affine);
+  if (film)
+    hipLaunchKernelGGL(gn_bwd_finalize_film_kernel, dim3((unsigned)groups), dim3(256), 0, s,
+                       pre_part ? pre_part : part, pre_part ? pre_nblk : (int)nb, C, (int)B, gamma, mr, groups, V,
+                       coef, dgamma, dbeta, acc_affine, film->beta, film->film, (long long)film->film_bs, film->dfilm,
+                       (long long)film->dfilm_bs);
+  else
+    hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3((unsigned)groups), dim3(256), 0, s, pre_part ? pre_part : part,
+                       pre_part ? pre_nblk : (int)nb, C, (int)B, gamma, mr, groups, V, coef, dgamma, dbeta, acc_affine);
   CWDM_LAUNCHED();
   // coef_out: reduce + finalize only; the caller fuses the apply into a
   // later kernel (cwdm::GapplyFuse) reading coef ([B][C][4]) from the workspace
   if (coef_out) {
-    CWDM_REQUIRE(!chs, CWDM_E_INVALID, "gn_silu_bwd: deferred apply with channel sums");
+    CWDM_REQUIRE(!chs && !(film && film->chs_c), CWDM_E_INVALID, "gn_silu_bwd: deferred apply with channel sums");
     *coef_out = coef;
     return CWDM_OK;
   }
@@ -807,7 +854,9 @@ int cwdm::gn_silu_bwd_impl(const void* x0, int c0, const void* x1, int c1, const
   if (nblk > 1024) nblk = 1024;
   dim3 grid((unsigned)nblk, (unsigned)B);
   const dim3 block((unsigned)(nvb * ncg));
-  float* cp = chs ? chs_part : nullptr;
+  // (a FiLM block: the sums over batch entries too, added to chs_c[c] -- its conv1's bias gradient)
+  float* const chs_c = film ? film->chs_c : nullptr;
+  float* cp = (chs || chs_c) ? chs_part : nullptr;
   if ((rc = dispatch_mode(du_mode, [&](auto M) -> int {
          constexpr int MD = decltype(M)::value;
          dispatch_dtype(dtype, [&](auto tag) -> int {
@@ -821,9 +870,9 @@ int cwdm::gn_silu_bwd_impl(const void* x0, int c0, const void* x1, int c1, const
          return CWDM_OK;
        })))
     return rc;
-  if (chs) {
+  if (chs || chs_c) {
     hipLaunchKernelGGL(chs_reduce_kernel, dim3((unsigned)ceil_div(C, 64)), dim3(1024), 0, s, chs_part, (int)nblk, C,
-                       chs, (long long)chs_stride, nullptr, nullptr, (int)B);
+                       chs, (long long)chs_stride, chs_c, nullptr, (int)B);
     CWDM_LAUNCHED();
   }
   return CWDM_OK;
@@ -835,6 +884,21 @@ extern "C" int cwdm_gn_silu_bwd(const void* x0, int c0, const void* x1, int c1, 
                                 float* dgamma, float* dbeta, void* ws, int64_t ws_bytes, cwdm_stream_t stream) {
   return gn_silu_bwd_impl(x0, c0, x1, c1, du, du_mode, ss, mr, gamma, groups, B, d, h, w, dtype, dx0, acc0, dx1, acc1,
                           dgamma, dbeta, ws, ws_bytes, nullptr, 0, stream, 0);
+}
+
+// cwdm_gn_silu_bwd of SiLU(GN(x) (1 + s) + t) (a FiLM ResBlock's out_layers.0): scale_shift is the folded
+// pair (cwdm_gn_finalize_film), film the rows [s | t] it was folded with; d s and d t are written to
+// dfilm + b * dfilm_bstride + [c | C + c]
+extern "C" int cwdm_gn_silu_bwd_film(const void* x0, int c0, const void* x1, int c1, const void* du, int du_mode,
+                                     const float* ss, const float* mr, const float* gamma, int groups, int64_t B,
+                                     int64_t d, int64_t h, int64_t w, int dtype, void* dx0, int acc0, void* dx1,
+                                     int acc1, float* dgamma, float* dbeta, void* ws, int64_t ws_bytes,
+                                     const float* beta, const float* film, int64_t film_bstride, float* dfilm,
+                                     int64_t dfilm_bstride, cwdm_stream_t stream) {
+  CWDM_REQUIRE(beta && film && dfilm, CWDM_E_INVALID, "cwdm_gn_silu_bwd_film: null pointer");
+  const GnBwdFilm f{beta, film, film_bstride, dfilm, dfilm_bstride, nullptr};
+  return gn_silu_bwd_impl(x0, c0, x1, c1, du, du_mode, ss, mr, gamma, groups, B, d, h, w, dtype, dx0, acc0, dx1, acc1,
+                          dgamma, dbeta, ws, ws_bytes, nullptr, 0, stream, 0, nullptr, 0, nullptr, &f);
 }
 
 extern "C" int cwdm_resample_add(void* dst, const void* src, int C, int64_t B, int64_t d, int64_t h, int64_t w,

@@ -157,11 +157,21 @@ int launch_emb_bwd(const float* dEb, int R, int n, int B, const float* temb, int
 int launch_temb_bwd(const float* t, int B, int mc, const float* w1, const float* b1, const float* w2,
                     const float* temb, const float* dsil, float* dw1, float* db1, float* dw2, float* db2,
                     hipStream_t s);
+// a FiLM block's out_layers.0 in gn_silu_bwd_impl: beta (d s needs it), the rows [s | t] and where d s, d t go
+// (batch strides in floats), and chs_c (optional): the per-channel sums of the written dx0 over voxels and
+// batch entries, added to chs_c[c] in a fixed order -- the bias gradient of the block's conv1
+struct GnBwdFilm {
+  const float* beta;
+  const float* film; int64_t film_bs;
+  float* dfilm; int64_t dfilm_bs;
+  float* chs_c;
+};
 int gn_silu_bwd_impl(const void* x0, int c0, const void* x1, int c1, const void* du, int du_mode, const float* ss,
                      const float* mr, const float* gamma, int groups, int64_t B, int64_t d, int64_t h, int64_t w,
                      int dtype, void* dx0, int acc0, void* dx1, int acc1, float* dgamma, float* dbeta, void* ws,
                      int64_t ws_bytes, float* chs, int64_t chs_stride, cwdm_stream_t stream, int acc_affine,
-                     const float* pre_part = nullptr, int pre_nblk = 0, const float** coef_out = nullptr);
+                     const float* pre_part = nullptr, int pre_nblk = 0, const float** coef_out = nullptr,
+                     const GnBwdFilm* film = nullptr);
 int gb_part_reduce(const float* part, int nblk, int C, int64_t B, int slices, float* out, hipStream_t s);
 // attention.hip: the bottleneck attention block's projections (cwdm_attn_linear / cwdm_attn_pack with
 // their arguments spelled out), the adjoint of the legacy row permutation for the qkv gradients

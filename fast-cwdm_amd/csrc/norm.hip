@@ -42,12 +42,14 @@ __device__ __forceinline__ void fin_segment(const float2* __restrict__ base, lon
   }
 }
 
-__global__ void __launch_bounds__(FIN_THREADS) gn_finalize_kernel(const float* __restrict__ s0, long long p0, int c0,
-                                                                 const float* __restrict__ s1, long long p1, int c1,
-                                                                 const float* __restrict__ gamma,
-                                                                 const float* __restrict__ beta, int groups,
-                                                                 long long voxels, float eps, float* __restrict__ out,
-                                                                 float* __restrict__ mean_rstd) {
+// FILM: the embedding rows [s | t] of batch entry b at film + b * film_bs folded into the pair (film_fold)
+template <bool FILM>
+__device__ __forceinline__ void gn_finalize_body(const float* __restrict__ s0, long long p0, int c0,
+                                                 const float* __restrict__ s1, long long p1, int c1,
+                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                 int groups, long long voxels, float eps, float* __restrict__ out,
+                                                 float* __restrict__ mean_rstd, const float* __restrict__ film,
+                                                 long long film_bs) {
   const int g = blockIdx.x, b = blockIdx.y;
   const int C = c0 + c1, cpg = C / groups;
   const int glo = g * cpg, ghi = glo + cpg;
@@ -88,10 +90,28 @@ __global__ void __launch_bounds__(FIN_THREADS) gn_finalize_kernel(const float* _
   }
   for (int ci = threadIdx.x; ci < cpg; ci += FIN_THREADS) {
     const int c = g * cpg + ci;
-    const float sc = gamma[c] * rstd;
+    float sc = gamma[c] * rstd;
+    float sh = beta[c] - meanf * sc;
+    if constexpr (FILM) film_fold(sc, sh, film[b * film_bs + c], film[b * film_bs + C + c]);
     out[((long long)b * C + c) * 2 + 0] = sc;
-    out[((long long)b * C + c) * 2 + 1] = beta[c] - meanf * sc;
+    out[((long long)b * C + c) * 2 + 1] = sh;
   }
+}
+
+__global__ void __launch_bounds__(FIN_THREADS) gn_finalize_kernel(const float* __restrict__ s0, long long p0, int c0,
+                                                                 const float* __restrict__ s1, long long p1, int c1,
+                                                                 const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, int groups,
+                                                                 long long voxels, float eps, float* __restrict__ out,
+                                                                 float* __restrict__ mean_rstd) {
+  gn_finalize_body<false>(s0, p0, c0, s1, p1, c1, gamma, beta, groups, voxels, eps, out, mean_rstd, nullptr, 0);
+}
+
+__global__ void __launch_bounds__(FIN_THREADS) gn_finalize_film_kernel(
+    const float* __restrict__ s0, long long p0, int c0, const float* __restrict__ s1, long long p1, int c1,
+    const float* __restrict__ gamma, const float* __restrict__ beta, int groups, long long voxels, float eps,
+    float* __restrict__ out, float* __restrict__ mean_rstd, const float* __restrict__ film, long long film_bs) {
+  gn_finalize_body<true>(s0, p0, c0, s1, p1, c1, gamma, beta, groups, voxels, eps, out, mean_rstd, film, film_bs);
 }
 
 }  // namespace
@@ -112,6 +132,28 @@ extern "C" int cwdm_gn_finalize(const float* s0, int64_t p0, int c0, const float
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(groups, (unsigned)B), dim3(FIN_THREADS), 0, (hipStream_t)stream, s0,
                      (long long)p0, c0, s1, (long long)p1, c1, gamma, beta, groups, (long long)voxels, eps, out,
                      mean_rstd);
+  CWDM_LAUNCHED();
+  return CWDM_OK;
+}
+
+// cwdm_gn_finalize of a FiLM ResBlock's out_layers.0 (use_scale_shift_norm): the pair becomes
+// (sc (1 + s), sh (1 + s) + t) with s = film[b * film_bstride + c], t = film[b * film_bstride + C + c]
+extern "C" int cwdm_gn_finalize_film(const float* s0, int64_t p0, int c0, const float* s1, int64_t p1, int c1,
+                                     const float* gamma, const float* beta, int groups, int64_t B, int64_t voxels,
+                                     float eps, float* out, float* mean_rstd, const float* film,
+                                     int64_t film_bstride, cwdm_stream_t stream) {
+  CWDM_REQUIRE(s0 && gamma && beta && out && film, CWDM_E_INVALID, "cwdm_gn_finalize_film: null pointer");
+  CWDM_REQUIRE(c1 == 0 || s1, CWDM_E_INVALID, "cwdm_gn_finalize_film: second source missing");
+  CWDM_REQUIRE(groups > 0 && (c0 + c1) % groups == 0, CWDM_E_SHAPE,
+               "cwdm_gn_finalize_film: channels must be divisible by num_groups");
+  CWDM_REQUIRE(B > 0 && B < 65536 && voxels > 0, CWDM_E_SHAPE, "cwdm_gn_finalize_film: bad batch/voxels");
+  CWDM_REQUIRE(p0 > 0 && p0 * c0 < (1LL << 31) && (c1 == 0 || (p1 > 0 && p1 * c1 < (1LL << 31))), CWDM_E_SHAPE,
+               "cwdm_gn_finalize_film: bad part count");
+  CWDM_REQUIRE(film_bstride >= 2 * (int64_t)(c0 + c1), CWDM_E_SHAPE,
+               "cwdm_gn_finalize_film: film rows need a batch stride of at least 2 C");
+  hipLaunchKernelGGL(gn_finalize_film_kernel, dim3(groups, (unsigned)B), dim3(FIN_THREADS), 0, (hipStream_t)stream,
+                     s0, (long long)p0, c0, s1, (long long)p1, c1, gamma, beta, groups, (long long)voxels, eps, out,
+                     mean_rstd, film, (long long)film_bstride);
   CWDM_LAUNCHED();
   return CWDM_OK;
 }

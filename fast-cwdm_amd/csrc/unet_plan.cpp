@@ -37,6 +37,8 @@ struct GnStep {
   int channels;
   int level;
   int ss_id;            // scale/shift buffer index
+  int film_row = -1;    // use_scale_shift_norm, a ResBlock's out_layers.0: row offset of its emb rows [scale | shift]
+                        // (folded into the scale/shift buffer by the finalize), -1: a plain GroupNorm
 };
 
 struct ConvStep {
@@ -341,11 +343,21 @@ void build(cwdm_unet* u) {
     }
     ConvStep c1{};
     conv_params(p + ".in_layers.2", cout, cin, 3, &c1.w_p, &c1.b_p);
-    c1.emb_w_p = addp(p + ".emb_layers.1.weight", {cout, E});
-    c1.emb_b_p = addp(p + ".emb_layers.1.bias", {cout});
+    // use_scale_shift_norm (unet.py ResBlock._forward): emb_out = [scale | shift] is applied after
+    // out_layers.0 (FiLM) instead of being added here, so conv1 keeps its own static bias
+    const bool film = c.use_scale_shift_norm != 0;
+    const int emb_n = film ? 2 * cout : cout;
+    c1.emb_w_p = addp(p + ".emb_layers.1.weight", {emb_n, E});
+    c1.emb_b_p = addp(p + ".emb_layers.1.bias", {emb_n});
     c1.a0 = a_src; c1.a1 = x1; c1.amode = a_mode; c1.gn = a_gn; c1.cin_a = cin;
     c1.sb0 = c1.sb1 = -1; c1.ws_p = c1.wsb_p = -1; c1.cin_b = 0;
-    c1.bias_kind = 1; c1.bias_off = add_emb_row(blk, c1.emb_w_p, c1.emb_b_p, c1.b_p, cout);
+    int film_row = -1;
+    if (film) {
+      c1.bias_kind = 0;
+      film_row = add_emb_row(blk, c1.emb_w_p, c1.emb_b_p, -1, emb_n);
+    } else {
+      c1.bias_kind = 1; c1.bias_off = add_emb_row(blk, c1.emb_w_p, c1.emb_b_p, c1.b_p, cout);
+    }
     c1.res = -1; c1.rmode = -1; c1.cout = cout; c1.level = lout; c1.stats = true;
     int h1 = c1.out = new_tensor(lout, cout);
     u->convs.push_back(c1);
@@ -354,6 +366,7 @@ void build(cwdm_unet* u) {
 
     int g2 = gn_step(p + ".out_layers.0", h1, -1, lout);
     blk.g2 = g2;
+    u->gns[g2].film_row = film_row;
     ConvStep c2{};
     conv_params(p + ".out_layers.3", cout, cout, 3, &c2.w_p, &c2.b_p);
     c2.a0 = h1; c2.a1 = -1; c2.amode = 0; c2.gn = g2; c2.cin_a = cout;
@@ -944,6 +957,8 @@ extern "C" int cwdm_unet_create(const cwdm_unet_config* cfg, cwdm_unet** plan) {
   }
   CWDM_REQUIRE(!(cfg->additive_skips && cfg->use_freq), CWDM_E_UNSUPPORTED,
                "cwdm_unet_create: additive_skips with use_freq (WavUNetModel has no concatenation to replace)");
+  CWDM_REQUIRE(!(cfg->use_scale_shift_norm && cfg->use_freq), CWDM_E_UNSUPPORTED,
+               "cwdm_unet_create: use_scale_shift_norm with use_freq (WavUNetModel's ResBlocks are not covered)");
   if (cfg->bottleneck_attention) {
     CWDM_REQUIRE(!cfg->use_freq, CWDM_E_UNSUPPORTED,
                  "cwdm_unet_create: bottleneck_attention with use_freq (WavUNetModel's middle block is not covered)");
@@ -1224,12 +1239,17 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
     f.ss = reinterpret_cast<float*>(wb + L.ss_off[g.ss_id]); f.mr = reinterpret_cast<float*>(wb + L.mr_off[g.ss_id]);
     f.B = B;
     f.used = false;
+    f.film = g.film_row >= 0 ? ebias + g.film_row : nullptr;
+    f.film_bs = u->R;
   };
   auto flush_fin = [&]() -> int {
     if (fin_pend < 0) return CWDM_OK;
     cwdm::GnFinFuse f{};
     fin_args(fin_pend, f);
     fin_pend = -1;
+    if (f.film)
+      return cwdm_gn_finalize_film(f.s0, f.p0, f.c0, f.s1, f.p1, f.c1, f.gamma, f.beta, f.groups, B, f.voxels, f.eps,
+                                   f.ss, f.mr, f.film, f.film_bs, stream);
     return cwdm_gn_finalize(f.s0, f.p0, f.c0, f.s1, f.p1, f.c1, f.gamma, f.beta, f.groups, B, f.voxels, f.eps, f.ss,
                             f.mr, stream);
   };
@@ -2126,7 +2146,22 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
       const int k = bk.emb_k;
       const int roff = u->emb_rows_off[k], rn = u->emb_rows_n[k];
       const bool fuse_sum = !u->ginit[h1];
-      if (fuse_sum) {
+      const bool film = u->gns[bk.g2].film_row >= 0;
+      if (film) {
+        // FiLM: the finalize writes d scale / d shift into the block's rows; conv1 has its own bias, whose
+        // gradient (the sum of dh1 over voxels and batch) is the apply pass's channel sums finished per channel
+        const auto& g = u->gns[bk.g2];
+        const float* ebias = reinterpret_cast<const float*>(wb + L.ebias);
+        cwdm::GnBwdFilm gf{P(g.beta_off), ebias + roff, u->R, deb + roff, u->R, fuse_sum ? GR(c1.b_p) : nullptr};
+        if ((rc = gn_silu_bwd_impl(act(h1), cout, nullptr, 0, tmp, 0, ss_of(bk.g2), mr_of(bk.g2), P(g.gamma_off),
+                                   u->cfg.num_groups, B, D >> lout, H >> lout, W >> lout, dt, grd(h1), take_acc(h1),
+                                   nullptr, 0, GR(g.gamma_p), GR(g.beta_p), gb + G.gnws, G.gnws_bytes, nullptr, 0,
+                                   stream, 1, pre2.part, pre2.nblk, nullptr, &gf)))
+          return rc;
+        if (!fuse_sum && (rc = cwdm_channel_sum(grd(h1), dt, B, Vo, cout, cout, nullptr, 0, GR(c1.b_p), nullptr,
+                                                gb + G.chs, G.chs_bytes, stream)))
+          return rc;
+      } else if (fuse_sum) {
         const auto& g = u->gns[bk.g2];
         if ((rc = gn_silu_bwd_impl(act(h1), cout, nullptr, 0, tmp, 0, ss_of(bk.g2), mr_of(bk.g2), P(g.gamma_off),
                                    u->cfg.num_groups, B, D >> lout, H >> lout, W >> lout, dt, grd(h1), take_acc(h1),
@@ -2141,7 +2176,8 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
       }
       // ---- conv1: emb projection, wgrad, dgrad
       if ((rc = launch_emb_bwd(deb + roff, u->R, rn, (int)B, temb, u->E, P(u->off_emb_w) + (int64_t)roff * u->E,
-                               GR(u->emb_rows_w[k]), GR(u->emb_rows_b[k]), GR(u->emb_rows_cb[k]), dsil, s, 1)))
+                               GR(u->emb_rows_w[k]), GR(u->emb_rows_b[k]),
+                               u->emb_rows_cb[k] >= 0 ? GR(u->emb_rows_cb[k]) : nullptr, dsil, s, 1)))
         return rc;
       if (bk.updown == 2) {
         const auto& ps = u->pools[bk.pool];

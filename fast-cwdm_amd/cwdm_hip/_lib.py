@@ -96,6 +96,7 @@ class UNetConfig(ctypes.Structure):
         ("mfma_split", ctypes.c_int), ("additive_skips", ctypes.c_int),
         ("bottleneck_attention", ctypes.c_int), ("num_heads", ctypes.c_int),
         ("num_head_channels", ctypes.c_int), ("attn_new_order", ctypes.c_int),
+        ("use_scale_shift_norm", ctypes.c_int),
     ]
 
 
@@ -180,6 +181,8 @@ _PROTOS = {
     "cwdm_conv3d_workspace_bytes": (i64, [ctypes.POINTER(ConvDesc)]),
     "cwdm_gn_finalize": (ctypes.c_int, [vp, i64, ctypes.c_int, vp, i64, ctypes.c_int, vp, vp, ctypes.c_int, i64, i64,
                                         ctypes.c_float, vp, vp, vp]),
+    "cwdm_gn_finalize_film": (ctypes.c_int, [vp, i64, ctypes.c_int, vp, i64, ctypes.c_int, vp, vp, ctypes.c_int, i64,
+                                             i64, ctypes.c_float, vp, vp, vp, i64, vp]),
     "cwdm_gn_silu_pool": (ctypes.c_int, [vp, ctypes.c_int, vp, i64, i64, i64, i64, ctypes.c_int, vp, vp, vp]),
     "cwdm_gn_apply": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, i64, i64, ctypes.c_int, vp, vp]),
     "cwdm_conv3d_set_path": (ctypes.c_int, [ctypes.c_int]),
@@ -192,6 +195,9 @@ _PROTOS = {
     "cwdm_device_status": (ctypes.c_int, [ctypes.c_int]),
     "cwdm_debug_gn_fin_apply": (ctypes.c_int, [vp, i64, ctypes.c_int, vp, i64, ctypes.c_int, vp, vp, ctypes.c_int,
                                                i64, i64, ctypes.c_float, vp, vp, ctypes.c_int, vp, vp, vp, vp]),
+    "cwdm_debug_gn_fin_apply_film": (ctypes.c_int, [vp, i64, ctypes.c_int, vp, i64, ctypes.c_int, vp, vp,
+                                                    ctypes.c_int, i64, i64, ctypes.c_float, vp, vp, ctypes.c_int,
+                                                    vp, vp, vp, vp, i64, vp]),
     "cwdm_debug_head2": (ctypes.c_int, [ctypes.c_int]),
     "cwdm_debug_pw_lt": (ctypes.c_int, [ctypes.c_int]),
     "cwdm_debug_conv_stamps": (ctypes.c_int, [vp]),
@@ -201,6 +207,9 @@ _PROTOS = {
     "cwdm_gn_silu_bwd": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp,
                                         ctypes.c_int, i64, i64, i64, i64, ctypes.c_int, vp, ctypes.c_int, vp,
                                         ctypes.c_int, vp, vp, vp, i64, vp]),
+    "cwdm_gn_silu_bwd_film": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp,
+                                             ctypes.c_int, i64, i64, i64, i64, ctypes.c_int, vp, ctypes.c_int, vp,
+                                             ctypes.c_int, vp, vp, vp, i64, vp, vp, i64, vp, i64, vp]),
     "cwdm_resample_add": (ctypes.c_int, [vp, vp, ctypes.c_int, i64, i64, i64, i64, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, vp]),
     "cwdm_channel_sum_workspace_bytes": (i64, [i64, i64, ctypes.c_int]),

@@ -31,7 +31,8 @@ def parse_dtype(d):
 class UNetPlan:
     def __init__(self, in_channels, model_channels, out_channels, num_res_blocks, channel_mult, num_groups,
                  dtype="fp32", resblock_updown=True, use_freq=False, additive_skips=False,
-                 bottleneck_attention=False, num_heads=1, num_head_channels=-1, use_new_attention_order=False):
+                 bottleneck_attention=False, num_heads=1, num_head_channels=-1, use_new_attention_order=False,
+                 use_scale_shift_norm=False):
         cfg = _lib.UNetConfig()
         cfg.in_channels, cfg.model_channels, cfg.out_channels = in_channels, model_channels, out_channels
         cfg.num_res_blocks, cfg.num_levels = num_res_blocks, len(channel_mult)
@@ -49,6 +50,7 @@ class UNetPlan:
         cfg.num_heads = int(num_heads)
         cfg.num_head_channels = int(num_head_channels)
         cfg.attn_new_order = 1 if use_new_attention_order else 0
+        cfg.use_scale_shift_norm = 1 if use_scale_shift_norm else 0
         self.use_freq = bool(use_freq)
         self.dtype = cfg.dtype
         self.torch_dtype = TORCH_DT[cfg.dtype]

@@ -11,7 +11,11 @@ compute dtype (``compute_dtype`` = "fp32" for reference numerics, "bf16" or
 bits); parameters stay fp32 masters and are re-packed when they change.
 
 Supported configuration family: the one run.sh uses (dims=3, no per-level
-attention, use_scale_shift_norm=False, resample_2d=False), with the skips
+attention, resample_2d=False), with the timestep embedding added to each
+ResBlock's first conv or, with use_scale_shift_norm=True (the reference's
+factory default), applied as FiLM after out_layers.0 (h = norm(h) * (1 + scale)
++ shift, folded into the norm's scale/shift table: no extra launch in the
+forward), with the skips
 concatenated or, with additive_skips=True, averaged into the decoder
 (h = (h + skip) / 2 as one ``cwdm_skip_avg`` pass per output block; run.sh's
 memory-saving switch), either resblock_updown=True (run.sh: ResBlock down/up) or
@@ -85,8 +89,6 @@ class UNetModel(nn.Module):
             unsupported.append("attention blocks")
         if not resblock_updown and not conv_resample:
             unsupported.append("resblock_updown=False with conv_resample=False (parameter-free pool / nearest layers)")
-        if use_scale_shift_norm:
-            unsupported.append("use_scale_shift_norm=True")
         if resample_2d:
             unsupported.append("resample_2d=True")
         if num_classes is not None:
@@ -100,14 +102,16 @@ class UNetModel(nn.Module):
                            attention_resolutions, dropout, channel_mult, conv_resample, num_classes, use_checkpoint,
                            num_heads, num_groups, resblock_updown, bottleneck_attention, additive_skips,
                            decoder_device_thresh, compute_dtype, num_head_channels=num_head_channels,
-                           use_new_attention_order=use_new_attention_order)
+                           use_new_attention_order=use_new_attention_order,
+                           use_scale_shift_norm=use_scale_shift_norm)
 
     use_freq = False
 
     def _setup_native(self, image_size, in_channels, model_channels, out_channels, num_res_blocks,
                       attention_resolutions, dropout, channel_mult, conv_resample, num_classes, use_checkpoint,
                       num_heads, num_groups, resblock_updown, bottleneck_attention, additive_skips,
-                      decoder_device_thresh, compute_dtype, num_head_channels=-1, use_new_attention_order=False):
+                      decoder_device_thresh, compute_dtype, num_head_channels=-1, use_new_attention_order=False,
+                      use_scale_shift_norm=False):
         self.image_size = image_size
         self.in_channels = in_channels
         self.model_channels = model_channels
@@ -122,6 +126,7 @@ class UNetModel(nn.Module):
         self.num_heads = num_heads
         self.num_head_channels = num_head_channels
         self.use_new_attention_order = bool(use_new_attention_order)
+        self.use_scale_shift_norm = bool(use_scale_shift_norm)
         self.num_groups = num_groups
         self.resblock_updown = bool(resblock_updown)
         self.bottleneck_attention = bottleneck_attention
@@ -250,7 +255,8 @@ class UNetModel(nn.Module):
                                         additive_skips=bool(self.additive_skips),
                                         bottleneck_attention=bool(self.bottleneck_attention),
                                         num_heads=self.num_heads, num_head_channels=self.num_head_channels,
-                                        use_new_attention_order=self.use_new_attention_order)
+                                        use_new_attention_order=self.use_new_attention_order,
+                                        use_scale_shift_norm=self.use_scale_shift_norm)
         return self._plans[key]
 
     @property

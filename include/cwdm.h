@@ -447,6 +447,17 @@ int cwdm_gn_finalize(const float* stats0, int64_t parts0, int c0,
                      int64_t B, int64_t voxels, float eps,
                      float* scale_shift, float* mean_rstd /* optional [B][groups][2] */,
                      cwdm_stream_t stream);
+/* The same for the out_layers.0 of a ResBlock with use_scale_shift_norm
+ * (guided_diffusion/unet.py ResBlock._forward: h = norm(h) * (1 + scale) + shift):
+ * film + b * film_bstride holds batch entry b's embedding row [scale (C) | shift (C)]
+ * (film_bstride >= 2 C floats), folded into the pair in fp32:
+ * scale' = scale (1 + s), shift' = shift (1 + s) + t.  mean_rstd as above. */
+int cwdm_gn_finalize_film(const float* stats0, int64_t parts0, int c0,
+                          const float* stats1, int64_t parts1, int c1,
+                          const float* gamma, const float* beta, int groups,
+                          int64_t B, int64_t voxels, float eps,
+                          float* scale_shift, float* mean_rstd /* optional [B][groups][2] */,
+                          const float* film, int64_t film_bstride, cwdm_stream_t stream);
 
 /* Down-ResBlock pre-pass: h = AvgPool2(SiLU(x*scale+shift)), x_upd = AvgPool2(x)
  * (ResBlock._forward with down=True, guided_diffusion/unet.py:286-291,
@@ -537,6 +548,13 @@ int cwdm_debug_gn_fin_apply(const float* stats0, int64_t parts0, int c0, const f
                             int c1, const float* gamma, const float* beta, int groups, int64_t B, int64_t voxels,
                             float eps, const void* x0, const void* x1, int dtype, float* scale_shift,
                             float* mean_rstd, void* out_cm, cwdm_stream_t stream);
+/* ... with the FiLM rows of cwdm_gn_finalize_film folded in (the same fold, so
+ * the fused and the unfused route round alike) */
+int cwdm_debug_gn_fin_apply_film(const float* stats0, int64_t parts0, int c0, const float* stats1, int64_t parts1,
+                                 int c1, const float* gamma, const float* beta, int groups, int64_t B,
+                                 int64_t voxels, float eps, const void* x0, const void* x1, int dtype,
+                                 float* scale_shift, float* mean_rstd, void* out_cm, const float* film,
+                                 int64_t film_bstride, cwdm_stream_t stream);
 
 /* Diagnostics / tests only: which output-head kernel runs -- 0 = the
  * second-generation head wherever its shape holds (64 input channels,
@@ -617,6 +635,18 @@ int cwdm_gn_silu_bwd(const void* x0, int c0, const void* x1, int c1, const void*
                      int64_t B, int64_t d, int64_t h, int64_t w, int dtype,
                      void* dx0, int acc0, void* dx1, int acc1, float* dgamma, float* dbeta,
                      void* workspace, int64_t ws_bytes, cwdm_stream_t stream);
+/* Backward of SiLU(GroupNorm(x) (1 + s) + t), the FiLM form of a ResBlock with
+ * use_scale_shift_norm: scale_shift is cwdm_gn_finalize_film's folded pair and
+ * film / film_bstride the rows it was folded with.  dgamma / dbeta are the
+ * affine's gradients (beta is read: d s needs it), and the rows' gradients go to
+ * dfilm + b * dfilm_bstride: [d s (C) | d t (C)] (overwritten).  Everything
+ * else as cwdm_gn_silu_bwd. */
+int cwdm_gn_silu_bwd_film(const void* x0, int c0, const void* x1, int c1, const void* du, int du_mode,
+                          const float* scale_shift, const float* mean_rstd, const float* gamma, int groups,
+                          int64_t B, int64_t d, int64_t h, int64_t w, int dtype,
+                          void* dx0, int acc0, void* dx1, int acc1, float* dgamma, float* dbeta,
+                          void* workspace, int64_t ws_bytes, const float* beta, const float* film,
+                          int64_t film_bstride, float* dfilm, int64_t dfilm_bstride, cwdm_stream_t stream);
 
 /* Adjoint of the resampling of a residual path: dst (grid d,h,w, C channels,
  * NDHWC, dtype) (+)= R^T src with mode 0 identity, 1 = src at the 2x grid
@@ -660,10 +690,13 @@ int cwdm_adamw_device_step(float* p, const float* g, float* m, float* v, int64_t
 /* ---------------------------------------------------------------------------
  * U-Net plan: the whole UNetModel.forward (guided_diffusion/unet.py:754-800)
  * for the run.sh configuration family (resblock_updown=True,
- * use_scale_shift_norm=False, resample_2d=False, dims=3; skips concatenated or,
- * with additive_skips, averaged: cwdm_skip_avg; no per-level attention, and
- * with bottleneck_attention the middle block's AttentionBlock:
- * cwdm_attention_forward between cwdm_attn_linear's two projections).
+ * resample_2d=False, dims=3; skips concatenated or, with additive_skips,
+ * averaged: cwdm_skip_avg; no per-level attention, and with
+ * bottleneck_attention the middle block's AttentionBlock:
+ * cwdm_attention_forward between cwdm_attn_linear's two projections; the
+ * embedding added to conv1's output or, with use_scale_shift_norm, applied as
+ * FiLM after out_layers.0: cwdm_gn_finalize_film folds it into the norm's
+ * scale / shift table, no launch added).
  * Topology and parameter names/shapes follow UNetModel.__init__
  * (unet.py:482-725) so reference state_dicts load unchanged.
  * ------------------------------------------------------------------------- */
@@ -691,6 +724,10 @@ typedef struct {
   int num_heads;            /* heads of that block when num_head_channels <= 0 (0 reads as 1) */
   int num_head_channels;    /* > 0: heads = channels / num_head_channels */
   int attn_new_order;       /* use_new_attention_order: qkv rows [Q | K | V] instead of per head [q | k | v] */
+  int use_scale_shift_norm; /* 1: every ResBlock computes h = out_layers.0(h) * (1 + scale) + shift with
+                               scale, shift = chunk(emb_out, 2) instead of adding emb_out to conv1's output
+                               (unet.py ResBlock._forward); emb_layers.1 becomes Linear(E, 2 C_out).  Not with
+                               use_freq.  0 (and a zeroed struct): off */
 } cwdm_unet_config;
 
 int cwdm_unet_create(const cwdm_unet_config* cfg, cwdm_unet** plan);
