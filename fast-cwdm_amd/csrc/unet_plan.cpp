@@ -3,6 +3,10 @@
 // naming contract (state_dict keys/shapes), packs weights into the kernel
 // layouts and replays UNetModel.forward (unet.py:754-800) as a fixed list of
 // GroupNorm-finalize and fused conv launches on one stream.
+//
+// build() also records the model as a list of Blocks, each of one BlockKind:
+// the gradient segments of the training backward.  cwdm_unet_backward runs a
+// range of them, last block first, through struct Backward, one member per kind.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,6 +14,7 @@
 #include <mutex>
 #include <string>
 #include <cstdlib>
+#include <utility>
 #include <vector>
 
 #include "internal.hpp"
@@ -101,19 +106,38 @@ enum StepKind { kGn, kConv, kPool /* pre-pass */, kS2d /* space-to-depth */, kHa
                 kAttn /* bottleneck attention */ };
 struct Step { StepKind kind; int idx; };
 
-// one ResBlock, for the backward (reverse order) and the gradient segments
+// what one Block is: the backward runs one function per kind (struct Backward)
+enum class BlockKind {
+  Res,         // ResBlock at one resolution (g1, c1, g2, c2)
+  ResUp,       // ResBlock(up=True): nearest x2 of its input folded into conv1's gather and the residual
+  ResDown,     // ResBlock(down=True): 2x average pool of SiLU(GN1(x)) and of x ahead of conv1 (pool)
+  Downsample,  // resblock_updown=False: the stride-2 conv c1 over the space-to-depth input (s2d)
+  Upsample,    // resblock_updown=False: nearest x2 + conv c1
+  WavDown,     // WavUNetModel ResBlock that halves the grid by DWT after conv1 (hh, hx)
+  WavUp,       // WavUNetModel ResBlock that doubles it by IDWT after conv1 (hh, hx)
+  WavPyramid,  // WavUNetModel WaveletDownsample of the input pyramid's level x0: haar, then the conv c1
+  Attention    // the bottleneck AttentionBlock: attn, g1 = its norm, x0 = its input
+};
+
+// resampling of a ResBlock's input, as the convs' a_mode / res_mode, the wgrad's u_mode, cwdm_resample_add
+// and the GroupNorm backward's du_mode number it: 0 none, 1 nearest x2 up, 2 2x average pool down
+int resample_mode(BlockKind k) { return k == BlockKind::ResUp ? 1 : (k == BlockKind::ResDown ? 2 : 0); }
+
+// one backward segment: a ResBlock or one of the other BlockKinds, in forward order (the backward runs
+// them in reverse).  Every index is -1 where the kind has no such step.
 struct Block {
-  int g1, pool, c1, g2, c2;   // step indices (pool = -1 unless down)
-  int x0, x1;                 // input tensors (x1 = -1 unless decoder concat)
-  int updown;                 // 0 none, 1 up, 2 down; layers without a ResBlock (resblock_updown=False):
-                              // 3 Downsample stride-2 conv (c1, pool = its S2dStep), 4 Upsample nearest + conv (c1);
-                              // WavUNetModel ResBlocks: 5 down (DWT), 6 up (IDWT); 7 WaveletDownsample of the input
-                              // pyramid (pool = its HaarStep, c1 = its conv, x0 = the pyramid level it transforms);
-                              // 8 the bottleneck AttentionBlock (pool = its AttnStep, g1 = its norm, x0 = its input)
-  int p_begin, p_end;         // parameter index range
-  int emb_k;                  // index into emb_rows_*
-  int hh = -1, hx = -1;       // WavUNetModel down / up blocks: HaarSteps of h (+ emb) and of x (x_upd)
-  int avg = -1;               // additive skips: the AvgStep that produced x0 (its adjoint ends the block's backward)
+  BlockKind kind = BlockKind::Res;
+  int g1 = -1, c1 = -1, g2 = -1, c2 = -1;  // u->gns / u->convs
+  int pool = -1;                           // u->pools (ResDown)
+  int s2d = -1;                            // u->s2ds (Downsample)
+  int haar = -1;                           // u->haars (WavPyramid)
+  int attn = -1;                           // u->attns (Attention)
+  int x0 = -1, x1 = -1;                    // input tensors (x1 = -1 unless decoder concat)
+  int p_begin = 0, p_end = 0;              // parameter index range
+  int emb_k = -1;                          // index into emb_rows_*
+  int hh = -1, hx = -1;                    // u->haars, WavDown / WavUp: the resampling of h (+ emb) and of x (x_upd)
+  int avg = -1;                            // u->avgs, additive skips: the step that produced x0 (its adjoint ends
+                                           // the block's backward)
 };
 
 }  // namespace
@@ -261,22 +285,23 @@ void build(cwdm_unet* u) {
     return row;
   };
 
-  // ResBlock (unet.py:185-311): returns output tensor.  updown 5 / 6: the
+  // ResBlock (unet.py:185-311): returns output tensor.  WavDown / WavUp: the
   // WavUNetModel ResBlock (wunet.py:210-269) that down/upsamples by DWT / IDWT
   // AFTER its first conv; skip_bands = the 7 high bands an up block inverts
   // with, *skip_out = the 7 high bands a down block returns.
-  auto resblock = [&](const std::string& p, int x0, int x1, int cout, int updown, int skip_bands = -1,
+  using BK = BlockKind;
+  auto resblock = [&](const std::string& p, int x0, int x1, int cout, BlockKind kind, int skip_bands = -1,
                       int* skip_out = nullptr) {
     Block blk{};
     blk.p_begin = (int)u->params.size();
-    blk.x0 = x0; blk.x1 = x1; blk.updown = updown; blk.pool = -1;
+    blk.x0 = x0; blk.x1 = x1; blk.kind = kind;
     const int lin = u->tensors[x0].level;
     const int cin = u->tensors[x0].channels + (x1 >= 0 ? u->tensors[x1].channels : 0);
-    const int lout = (updown == 2 || updown == 5) ? lin + 1 : ((updown == 1 || updown == 6) ? lin - 1 : lin);
+    const bool down = kind == BK::ResDown || kind == BK::WavDown, up = kind == BK::ResUp || kind == BK::WavUp;
+    const int lout = down ? lin + 1 : (up ? lin - 1 : lin);
     int g1 = gn_step(p + ".in_layers.0", x0, x1, lin);
     blk.g1 = g1;
-    if (updown >= 5) {
-      const bool down = updown == 5;
+    if (kind == BK::WavDown || kind == BK::WavUp) {
       ConvStep c1{};
       conv_params(p + ".in_layers.2", cout, cin, 3, &c1.w_p, &c1.b_p);
       c1.emb_w_p = addp(p + ".emb_layers.1.weight", {cout, E});
@@ -327,9 +352,9 @@ void build(cwdm_unet* u) {
       u->blocks.push_back(blk);
       return o;
     }
-    int xres = x0, xrmode = updown == 2 ? 2 : (updown == 1 ? 1 : 0);
-    int a_src = x0, a_mode = updown, a_gn = g1;
-    if (updown == 2) {
+    int xres = x0, xrmode = resample_mode(kind);
+    int a_src = x0, a_mode = resample_mode(kind), a_gn = g1;
+    if (kind == BK::ResDown) {
       // AvgPool(SiLU(GN(x))) and AvgPool(x) once, at the low resolution
       PoolStep ps{};
       ps.src = x0; ps.ss_id = g1; ps.level_out = lout; ps.channels = cin;
@@ -396,7 +421,7 @@ void build(cwdm_unet* u) {
   auto resample_layer = [&](const std::string& p, int x, int down) {
     Block blk{};
     blk.p_begin = (int)u->params.size();
-    blk.x0 = x; blk.x1 = -1; blk.updown = down ? 3 : 4; blk.pool = -1; blk.g1 = blk.g2 = blk.c2 = -1; blk.emb_k = -1;
+    blk.x0 = x; blk.kind = down ? BK::Downsample : BK::Upsample;
     const int lin = u->tensors[x].level, chn = u->tensors[x].channels;
     const int lout = down ? lin + 1 : lin - 1;
     ConvStep cs{};
@@ -407,7 +432,7 @@ void build(cwdm_unet* u) {
       S2dStep sd{x, new_tensor(lout, 8 * chn), lout, chn};
       u->s2ds.push_back(sd);
       u->steps.push_back({kS2d, (int)u->s2ds.size() - 1});
-      blk.pool = (int)u->s2ds.size() - 1;
+      blk.s2d = (int)u->s2ds.size() - 1;
       cs.a0 = sd.out; cs.amode = 0; cs.cin_a = 8 * chn; cs.s2 = 1;
     } else {
       cs.a0 = x; cs.amode = 1; cs.cin_a = chn;
@@ -432,13 +457,13 @@ void build(cwdm_unet* u) {
     for (int l = 0; l < nl; ++l) {
       const int mult = c.channel_mult[l];
       for (int r = 0; r < c.num_res_blocks; ++r) {
-        h = resblock("input_blocks." + std::to_string(idx) + ".0", h, -1, mult * mc, 0);
+        h = resblock("input_blocks." + std::to_string(idx) + ".0", h, -1, mult * mc, BK::Res);
         ch = mult * mc;
         u->trace.push_back(h); u->trace_level.push_back(level);
         ++idx;
       }
       int sk = -1;
-      h = resblock("input_blocks." + std::to_string(idx) + ".0", h, -1, ch, 5, -1, &sk);
+      h = resblock("input_blocks." + std::to_string(idx) + ".0", h, -1, ch, BK::WavDown, -1, &sk);
       skips.push_back(sk);
       ++level;
       u->trace.push_back(h); u->trace_level.push_back(level);
@@ -451,8 +476,7 @@ void build(cwdm_unet* u) {
       u->tensors[hp.out].stats_kind = -1;
       haar_step(hp);
       Block pb{};   // the WaveletDownsample as a backward segment of its own
-      pb.updown = 7; pb.pool = (int)u->haars.size() - 1; pb.x0 = pyr; pb.x1 = -1;
-      pb.g1 = pb.g2 = pb.c2 = -1; pb.emb_k = -1;
+      pb.kind = BK::WavPyramid; pb.haar = (int)u->haars.size() - 1; pb.x0 = pyr;
       pb.p_begin = (int)u->params.size();
       ConvStep cs{};
       conv_params("input_blocks." + std::to_string(idx + 1) + ".0.conv", ch, 8 * cp, 3, &cs.w_p, &cs.b_p);
@@ -468,9 +492,9 @@ void build(cwdm_unet* u) {
       u->trace.push_back(h); u->trace_level.push_back(level);
       idx += 2;
     }
-    h = resblock("middle_block.0", h, -1, ch, 0);
+    h = resblock("middle_block.0", h, -1, ch, BK::Res);
     u->trace.push_back(h); u->trace_level.push_back(level);
-    h = resblock("middle_block.1", h, -1, ch, 0);
+    h = resblock("middle_block.1", h, -1, ch, BK::Res);
     u->trace.push_back(h); u->trace_level.push_back(level);
     idx = 0;
     for (int l = nl - 1; l >= 0; --l) {
@@ -481,16 +505,16 @@ void build(cwdm_unet* u) {
       for (int i = 0; i <= c.num_res_blocks; ++i) {
         const std::string p = "output_blocks." + std::to_string(idx);
         if (i != c.num_res_blocks) {
-          h = resblock(p + ".0", h, -1, mc * mult, 0);
+          h = resblock(p + ".0", h, -1, mc * mult, BK::Res);
           ch = mc * mult;
           owner = p + ".0";
         } else {
           // Sequential(<the level's last ResBlock again>, IDWT ResBlock)
           alias_from = p + ".0.";
           alias_to = owner + ".";
-          h = resblock(p + ".0", h, -1, ch, 0);
+          h = resblock(p + ".0", h, -1, ch, BK::Res);
           alias_from.clear();
-          h = resblock(p + ".1", h, -1, ch, 6, sk);
+          h = resblock(p + ".1", h, -1, ch, BK::WavUp, sk);
           --level;
         }
         u->trace.push_back(h); u->trace_level.push_back(level);
@@ -498,14 +522,14 @@ void build(cwdm_unet* u) {
       }
     }
     for (int i = 0; i < c.num_res_blocks; ++i) {
-      h = resblock("out_res." + std::to_string(i) + ".0", h, -1, ch, 0);
+      h = resblock("out_res." + std::to_string(i) + ".0", h, -1, ch, BK::Res);
       u->trace.push_back(h); u->trace_level.push_back(level);
     }
   }
   for (int l = 0; l < nl && !c.use_freq; ++l) {
     const int mult = c.channel_mult[l];
     for (int r = 0; r < c.num_res_blocks; ++r) {
-      h = resblock("input_blocks." + std::to_string(idx) + ".0", h, -1, mult * mc, 0);
+      h = resblock("input_blocks." + std::to_string(idx) + ".0", h, -1, mult * mc, BK::Res);
       ch = mult * mc;
       stack.push_back(h);
       u->trace.push_back(h); u->trace_level.push_back(level);
@@ -513,7 +537,7 @@ void build(cwdm_unet* u) {
     }
     if (l != nl - 1) {
       const std::string p = "input_blocks." + std::to_string(idx) + ".0";
-      h = c.resblock_updown ? resblock(p, h, -1, ch, 2) : resample_layer(p + ".op", h, 1);
+      h = c.resblock_updown ? resblock(p, h, -1, ch, BK::ResDown) : resample_layer(p + ".op", h, 1);
       ++level;
       stack.push_back(h);
       u->trace.push_back(h); u->trace_level.push_back(level);
@@ -521,14 +545,14 @@ void build(cwdm_unet* u) {
     }
   }
   if (!c.use_freq) {
-    h = resblock("middle_block.0", h, -1, ch, 0);
+    h = resblock("middle_block.0", h, -1, ch, BK::Res);
     u->trace.push_back(h); u->trace_level.push_back(level);
     if (c.bottleneck_attention) {
       // AttentionBlock (unet.py:314-360): norm, qkv, proj_out in state_dict order; the ResBlock after it
       // is then middle_block.2
       Block blk{};
       blk.p_begin = (int)u->params.size();
-      blk.x0 = h; blk.x1 = -1; blk.updown = 8; blk.c1 = blk.c2 = blk.g2 = -1; blk.emb_k = -1;
+      blk.x0 = h; blk.kind = BK::Attention;
       AttnStep at{};
       at.src = h; at.level = level; at.C = ch;
       at.heads = c.num_head_channels > 0 ? ch / c.num_head_channels : std::max(c.num_heads, 1);
@@ -542,12 +566,12 @@ void build(cwdm_unet* u) {
       u->tensors[h].stats_kind = 4;
       u->attns.push_back(at);
       u->steps.push_back({kAttn, (int)u->attns.size() - 1});
-      blk.pool = (int)u->attns.size() - 1;
+      blk.attn = (int)u->attns.size() - 1;
       blk.p_end = (int)u->params.size();
       u->blocks.push_back(blk);
       u->trace.push_back(h); u->trace_level.push_back(level);
     }
-    h = resblock(c.bottleneck_attention ? "middle_block.2" : "middle_block.1", h, -1, ch, 0);
+    h = resblock(c.bottleneck_attention ? "middle_block.2" : "middle_block.1", h, -1, ch, BK::Res);
     u->trace.push_back(h); u->trace_level.push_back(level);
     idx = 0;
   }
@@ -565,16 +589,16 @@ void build(cwdm_unet* u) {
         u->avgs.push_back(as);
         u->steps.push_back({kAvg, (int)u->avgs.size() - 1});
         ch = stack.empty() ? mc : u->tensors[stack.back()].channels;
-        h = resblock("output_blocks." + std::to_string(idx) + ".0", as.out, -1, ch, 0);
+        h = resblock("output_blocks." + std::to_string(idx) + ".0", as.out, -1, ch, BK::Res);
         u->blocks.back().avg = (int)u->avgs.size() - 1;
       } else {
-        h = resblock("output_blocks." + std::to_string(idx) + ".0", h, skip, mc * mult, 0);
+        h = resblock("output_blocks." + std::to_string(idx) + ".0", h, skip, mc * mult, BK::Res);
         ch = mc * mult;
       }
       u->trace.push_back(h); u->trace_level.push_back(level);
       if (l && i == c.num_res_blocks) {
         const std::string p = "output_blocks." + std::to_string(idx) + ".1";
-        h = c.resblock_updown ? resblock(p, h, -1, ch, 1) : resample_layer(p + ".conv", h, 0);
+        h = c.resblock_updown ? resblock(p, h, -1, ch, BK::ResUp) : resample_layer(p + ".conv", h, 0);
         --level;
         u->trace.push_back(h); u->trace_level.push_back(level);
       }
@@ -1174,6 +1198,19 @@ extern "C" double cwdm_unet_flops(const cwdm_unet* u, int64_t B, int64_t D, int6
   return f;
 }
 
+// the attention block's descriptor, forward part: q, k, v side by side in the rows of qkv (B, T, 3 C), the
+// output rows in a (B, T, C), the rows' log-sum-exp in lse (nullptr: not kept)
+static cwdm_attention_desc attn_desc(const AttnStep& at, int dt, int64_t B, int64_t T, const unsigned char* qkv,
+                                     void* a, float* lse) {
+  const int64_t C = at.C, es = esize(dt);
+  cwdm_attention_desc ad{};
+  ad.dtype = dt; ad.B = B; ad.T = T; ad.heads = at.heads; ad.ch = at.ch;
+  ad.q = qkv; ad.k = qkv + C * es; ad.v = qkv + 2 * C * es;
+  ad.q_rs = ad.k_rs = ad.v_rs = 3 * C; ad.q_bs = ad.k_bs = ad.v_bs = T * 3 * C;
+  ad.o = a; ad.o_rs = C; ad.o_bs = T * C; ad.L = lse;
+  return ad;
+}
+
 // samp: run the sampling step on the output (cwdm_unet_forward_step); fused
 // into the output head when it qualifies (*fused = 1), else after the forward.
 static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, const float* t, float* out,
@@ -1304,19 +1341,15 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
       // (the norm's finalize ran just above: no conv takes it)
       const auto& at = u->attns[st.idx];
       const int64_t T = (D >> at.level) * (H >> at.level) * (W >> at.level);
-      const int dt = u->cfg.dtype, es = esize(dt), C = at.C;
+      const int dt = u->cfg.dtype, C = at.C;
       unsigned char* qkv = wb + L.attn_qkv;
       void* a = wb + L.attn_a;
       if ((rc = cwdm::attn_linear(dt, B, T, C, 3 * C, tptr(at.src), reinterpret_cast<const float*>(wb + L.ss_off[at.gn]),
                                   pk + at.qkv_w_off, P(at.qkv_b_off), nullptr, qkv, keep ? wb + L.attn_n : nullptr,
                                   nullptr, s)))
         return rc;
-      cwdm_attention_desc ad{};
-      ad.dtype = dt; ad.B = B; ad.T = T; ad.heads = at.heads; ad.ch = at.ch;
-      ad.q = qkv; ad.k = qkv + (int64_t)C * es; ad.v = qkv + (int64_t)2 * C * es;
-      ad.q_rs = ad.k_rs = ad.v_rs = 3 * C; ad.q_bs = ad.k_bs = ad.v_bs = T * 3 * C;
-      ad.o = a; ad.o_rs = C; ad.o_bs = T * C;
-      ad.L = keep ? reinterpret_cast<float*>(wb + L.attn_L) : nullptr;
+      const cwdm_attention_desc ad =
+          attn_desc(at, dt, B, T, qkv, a, keep ? reinterpret_cast<float*>(wb + L.attn_L) : nullptr);
       if ((rc = cwdm_attention_forward(&ad, stream))) return rc;
       if ((rc = cwdm::attn_linear(dt, B, T, C, C, a, nullptr, pk + at.proj_w_off, P(at.proj_b_off), tptr(at.src),
                                   wb + L.t_off[at.out], nullptr, reinterpret_cast<float*>(wb + L.s_off[at.out]), s)))
@@ -1539,6 +1572,8 @@ extern "C" int cwdm_unet_profile_read(cwdm_unet* u, double* ms, double* flops, i
 //   GN1:   SiLU/GroupNorm backward with the up/down resample adjoint -> dx
 // Gradient buffers live in grad_ws (one per forward tensor, compute dtype);
 // the first writer of a buffer stores, later writers accumulate.
+// Segment 0 is the output head, then one per Block from the last to the first
+// (by BlockKind, the members of struct Backward), then conv_in + time_embed.
 // ============================================================================
 namespace {
 
@@ -1719,112 +1754,102 @@ extern "C" double cwdm_unet_backward_flops(const cwdm_unet* u, int64_t B, int64_
   return f;
 }
 
-extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* packed_bwd, const void* x,
-                                  const float* t, const float* dout, float* grads, int64_t B, int64_t D, int64_t H,
-                                  int64_t W, const void* ws, int64_t ws_bytes, void* gws, int64_t gws_bytes,
-                                  int seg_begin, int seg_end, cwdm_stream_t stream) {
-  CWDM_REQUIRE(u && packed && packed_bwd && x && t && dout && grads && ws && gws, CWDM_E_INVALID,
-               "cwdm_unet_backward: null pointer");
-  const int nseg = (int)u->blocks.size() + 2;
-  CWDM_REQUIRE(0 <= seg_begin && seg_begin <= seg_end && seg_end <= nseg, CWDM_E_INVALID,
-               "cwdm_unet_backward: bad segment range");
-  CWDM_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, CWDM_E_SHAPE, "cwdm_unet_backward: empty grid");
-  const int64_t div = int64_t(1) << (u->cfg.num_levels - (u->cfg.use_freq ? 0 : 1));
-  CWDM_REQUIRE(D % div == 0 && H % div == 0 && W % div == 0, CWDM_E_SHAPE,
-               "cwdm_unet_backward: every subband edge must be divisible by " + std::to_string(div));
-  Layout L = layout(u, B, D, H, W);
-  GLayout G = glayout(u, B, D, H, W);
-  CWDM_REQUIRE(ws_bytes >= L.total, CWDM_E_WORKSPACE, "cwdm_unet_backward: forward workspace too small");
-  CWDM_REQUIRE(gws_bytes >= G.total, CWDM_E_WORKSPACE,
-               "cwdm_unet_backward: grad workspace too small (need " + std::to_string(G.total) + " bytes)");
-  CWDM_REQUIRE(seg_begin == 0 || (int)u->ginit.size() == (int)u->tensors.size(), CWDM_E_INVALID,
-               "cwdm_unet_backward: segment 0 must run first");
+namespace {
+
+// the reduce pass of a GroupNorm backward that a dgrad conv's epilogue took (Backward::dgrad_gn): its partials
+struct Pre { const float* part = nullptr; int nblk = 0; };
+// what Backward::gn_bwd does beyond the plain backward
+struct GnBwdOpt {
+  float* chs = nullptr; int64_t chs_stride = 0;   // per-batch channel sums of the written dx0, in the same pass
+  const cwdm::GnBwdFilm* film = nullptr;   // a FiLM block's out_layers.0
+  const float** coef_out = nullptr;        // reduce / finalize only: the apply pass's coefficients for a GapplyFuse
+  bool keep_acc = false;                   // with coef_out: leave the store / accumulate state to the conv that applies
+};
+
+// One cwdm_unet_backward call: what its launches read, the calls they share, and one member per kind of
+// segment.  Everything goes out on one stream and shares the scratch regions tmp (a dgrad's output = the
+// GroupNorm backward's input), G.chs, G.gnws, G.wgws and G.split, so a segment's launch order is part of its
+// result.  The store / accumulate state of the gradient buffers (u->ginit, take_acc) lives in the plan: it
+// carries over between calls that each run a range of segments.
+struct Backward {
+  cwdm_unet* u;
+  const Layout& L;
+  const GLayout& G;
+  const unsigned char *pk, *pb, *wb;   // packed parameters (forward, backward form), the forward's workspace
+  unsigned char* gb;                   // the gradient workspace
+  const void* x; const float *t, *dout; float* grads;
+  int64_t B, D, H, W;
+  bool kept;   // the forward ran on a training-sized workspace: the convs' activated inputs are there
+  cwdm_stream_t stream;
+  // derived from the above
   hipStream_t s = (hipStream_t)stream;
-  const int dt = u->cfg.dtype;
-  const int es = esize(dt);
-  auto* pk = reinterpret_cast<const unsigned char*>(packed);
-  auto* pb = reinterpret_cast<const unsigned char*>(packed_bwd);
-  auto* wb = reinterpret_cast<const unsigned char*>(ws);
-  auto* gb = reinterpret_cast<unsigned char*>(gws);
-  // (every call: a caller may run segments on a fresh grad workspace)
-  CWDM_HIP(hipMemsetAsync(gb + G.sync, 0, cwdm::plan_sync_bytes(), s));
-  unsigned* const sync = reinterpret_cast<unsigned*>(gb + G.sync);
-  auto P = [&](int64_t off) { return reinterpret_cast<const float*>(pk + off); };
-  auto GR = [&](int pi) { return grads + u->goff[pi]; };
-  auto act = [&](int id) -> const void* {
-    if (id < 0) return nullptr;
-    if (id == u->input_tensor) return x;
-    return wb + L.t_off[id];
-  };
-  auto grd = [&](int id) -> void* { return id < 0 ? nullptr : gb + G.g_off[id]; };
-  auto vox = [&](int lv) { return (D >> lv) * (H >> lv) * (W >> lv); };
+  int dt = u->cfg.dtype, es = esize(dt);
+  unsigned* sync = reinterpret_cast<unsigned*>(gb + G.sync);   // the zeroed sync block (ConvCall::sync)
   const float* temb = reinterpret_cast<const float*>(wb + L.temb);
-  float* deb = reinterpret_cast<float*>(gb + G.deb);
-  float* dsil = reinterpret_cast<float*>(gb + G.dsil);
+  float* deb = reinterpret_cast<float*>(gb + G.deb);     // d emb projection rows [B][R]
+  float* dsil = reinterpret_cast<float*>(gb + G.dsil);   // d SiLU(time embedding) [B][E]
   void* tmp = gb + G.tmp;
-  int rc;
+  float* gbp = reinterpret_cast<float*>(gb + G.gbp);
 
+  const float* P(int64_t off) const { return reinterpret_cast<const float*>(pk + off); }
+  float* GR(int pi) const { return grads + u->goff[pi]; }
+  const void* act(int id) const { return id < 0 ? nullptr : (id == u->input_tensor ? x : wb + L.t_off[id]); }
+  void* grd(int id) const { return id < 0 ? nullptr : gb + G.g_off[id]; }
+  int nch(int id) const { return id < 0 ? 0 : u->tensors[id].channels; }
+  int64_t vox(int lv) const { return (D >> lv) * (H >> lv) * (W >> lv); }
+  const float* ss_of(int g) const { return reinterpret_cast<const float*>(wb + L.ss_off[g]); }
+  const float* mr_of(int g) const { return reinterpret_cast<const float*>(wb + L.mr_off[g]); }
   // first writer stores, later writers accumulate
-  auto take_acc = [&](int id) -> int {
-    if (id < 0) return 0;
-    const int a = u->ginit[id] ? 1 : 0;
-    u->ginit[id] = 1;
-    return a;
-  };
-  auto ss_of = [&](int g) { return reinterpret_cast<const float*>(wb + L.ss_off[g]); };
-  auto mr_of = [&](int g) { return reinterpret_cast<const float*>(wb + L.mr_off[g]); };
+  int take_acc(int id) { return id < 0 ? 0 : (std::exchange(u->ginit[id], char(1)) ? 1 : 0); }
 
-  auto wgrad = [&](int level, int ksize, const void* u0, int uc0, const void* u1, int uc1, int umode,
-                   const float* ugn, const void* dy, int dy_cs, int cout, float* dw) -> int {
+  // bias gradient of a conv / linear layer: the channel sums of its output gradient dy (B, voxels of level,
+  // stride channels, the first C of them summed) into db, and into db2 (a folded-in second bias) if given
+  int bias_grad(const void* dy, int level, int C, float* db, float* db2 = nullptr, int stride = 0) {
+    return cwdm_channel_sum(dy, dt, B, vox(level), C, stride ? stride : C, nullptr, 0, db, db2, gb + G.chs,
+                            G.chs_bytes, stream);
+  }
+  // the gradient of tensor id (at level lv) takes src through the adjoint of resample mode
+  int resample_add(int id, const void* src, int C, int lv, int mode) {
+    return cwdm_resample_add(grd(id), src, C, B, D >> lv, H >> lv, W >> lv, mode, take_acc(id), dt, stream);
+  }
+  // weight gradient dw of a conv (u_cm: u0 is an activated input in the chunk-major form a forward conv kept)
+  int wgrad(int level, int ksize, const void* u0, int uc0, const void* u1, int uc1, int umode, const float* ugn,
+            const void* dy, int dy_cs, int cout, float* dw, int u_cm = 0) {
     cwdm_wgrad_desc d{};
     d.dtype = dt; d.B = B; d.D = D >> level; d.H = H >> level; d.W = W >> level; d.ksize = ksize;
-    d.u0 = u0; d.u_c0 = uc0; d.u1 = u1; d.u_c1 = uc1; d.u_mode = umode; d.u_gn = ugn;
+    d.u0 = u0; d.u_c0 = uc0; d.u1 = u1; d.u_c1 = uc1; d.u_mode = umode; d.u_gn = ugn; d.u_cm = u_cm;
     d.dy = dy; d.dy_cs = dy_cs; d.cout = cout; d.dw = dw;
-    d.workspace = gb + G.wgws;
-    d.ws_bytes = G.wgws_bytes;
+    d.workspace = gb + G.wgws; d.ws_bytes = G.wgws_bytes;
     return cwdm_conv3d_wgrad(&d, stream);
-  };
+  }
   // conv ci's wgrad from the activated input its forward kept (training
   // workspace), else recomputed from the sources by the staging code
-  const bool kept = L.train_total > L.total && ws_bytes >= L.train_total;
-  auto wgrad_c = [&](int ci, int level, const void* u0, int uc0, const void* u1, int uc1, int umode,
-                     const float* ugn, const void* dy, int dy_cs, int cout, float* dw) -> int {
+  int wgrad_c(int ci, int level, const void* u0, int uc0, const void* u1, int uc1, int umode, const float* ugn,
+              const void* dy, int dy_cs, int cout, float* dw) {
     if (!kept || L.keep_off[ci] < 0) return wgrad(level, 3, u0, uc0, u1, uc1, umode, ugn, dy, dy_cs, cout, dw);
-    cwdm_wgrad_desc d{};
-    d.dtype = dt; d.B = B; d.D = D >> level; d.H = H >> level; d.W = W >> level; d.ksize = 3;
-    d.u0 = wb + L.keep_off[ci]; d.u_c0 = uc0 + uc1; d.u_mode = umode; d.u_cm = 1;
-    d.dy = dy; d.dy_cs = dy_cs; d.cout = cout; d.dw = dw;
-    d.workspace = gb + G.wgws;
-    d.ws_bytes = G.wgws_bytes;
-    return cwdm_conv3d_wgrad(&d, stream);
-  };
-  auto dgrad = [&](int ci, const void* dy, cwdm::GbwdFuse* gbwd = nullptr) -> int {
+    return wgrad(level, 3, wb + L.keep_off[ci], uc0 + uc1, nullptr, 0, umode, nullptr, dy, dy_cs, cout, dw, 1);
+  }
+  // input gradient of conv ci into tmp
+  int dgrad(int ci, const void* dy, cwdm::GbwdFuse* gbwd = nullptr) {
     cwdm_conv3d_desc d = dgrad_shape(u, ci, B, D, H, W);
-    d.a0 = dy;
-    d.a_w = pb + u->dg_off[ci];
-    d.out = tmp;
-    d.workspace = gb + G.split;
-    d.ws_bytes = G.split_bytes;
+    d.a0 = dy; d.a_w = pb + u->dg_off[ci]; d.out = tmp;
+    d.workspace = gb + G.split; d.ws_bytes = G.split_bytes;
     cwdm::ConvCall cc;
-    cc.sync = sync;
-    cc.gbwd = gbwd;
+    cc.sync = sync; cc.gbwd = gbwd;
     return cwdm::conv3d_forward(&d, cc, s);
-  };
+  }
   // dgrad conv ci whose output du (tmp) feeds the SiLU(GroupNorm gi) backward at
   // the same grid, input x = (xid0, xid1): the conv's epilogue takes the reduce
   // pass of that backward when its kernel can (cwdm::GbwdFuse: 16-bit DMA conv,
-  // no K split); pre then names the partials for gn_silu_bwd_impl
-  struct Pre { const float* part = nullptr; int nblk = 0; };
-  static const bool gb_on = env_not0("CWDM_GBWD_FUSE");
-  float* gbp = reinterpret_cast<float*>(gb + G.gbp);
-  auto dgrad_gn = [&](int ci, const void* dy, int gi, int xid0, int xid1, Pre& pre) -> int {
+  // no K split); pre then names the partials for gn_bwd
+  int dgrad_gn(int ci, const void* dy, int gi, int xid0, int xid1, Pre& pre) {
     pre = Pre{};
+    static const bool gb_on = env_not0("CWDM_GBWD_FUSE");
     if (!gb_on || G.gbp_bytes <= 0) return dgrad(ci, dy);
     const auto& g = u->gns[gi];
     cwdm::GbwdFuse f{};
-    f.x0 = act(xid0); f.x1 = act(xid1); f.c0 = u->tensors[xid0].channels;
-    f.ss = ss_of(gi); f.mr = mr_of(gi); f.groups = u->cfg.num_groups;
-    f.part = gbp;
+    f.x0 = act(xid0); f.x1 = act(xid1); f.c0 = nch(xid0);
+    f.ss = ss_of(gi); f.mr = mr_of(gi); f.groups = u->cfg.num_groups; f.part = gbp;
     f.part_bytes = G.gbp_bytes - align_up(B * (int64_t)kGbSlices * g.channels * 8);
     const int r = dgrad(ci, dy, &f);
     if (r || !f.used) return r;
@@ -1836,398 +1861,370 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
     if (int rc2 = gb_part_reduce(gbp, f.nblk, g.channels, B, kGbSlices, sl, s)) return rc2;
     pre.part = sl; pre.nblk = kGbSlices;
     return CWDM_OK;
-  };
-  auto gn_bwd = [&](int gi, int x0, int x1, int du_mode, const Pre* pre = nullptr) -> int {
+  }
+  // SiLU(GroupNorm gi) backward of du = tmp (du_mode: resample_mode of the block) into the gradients of the
+  // norm's input (x0, x1), its reduce pass in pre if the dgrad took it; the only gn_silu_bwd_impl call here
+  int gn_bwd(int gi, int x0, int x1, int du_mode, const Pre& pre, const GnBwdOpt& o = {}) {
     const auto& g = u->gns[gi];
     const int lv = g.level;
-    const int c0 = u->tensors[x0].channels, c1 = x1 >= 0 ? u->tensors[x1].channels : 0;
-    const int a0 = take_acc(x0), a1 = take_acc(x1);
+    const int a0 = o.keep_acc ? 0 : take_acc(x0), a1 = o.keep_acc ? 0 : take_acc(x1);
     // affine gradients accumulate (zeroed at segment 0): a reused WavUNetModel block adds its second use
-    return gn_silu_bwd_impl(act(x0), c0, act(x1), c1, tmp, du_mode, ss_of(gi), mr_of(gi), P(g.gamma_off),
+    return gn_silu_bwd_impl(act(x0), nch(x0), act(x1), nch(x1), tmp, du_mode, ss_of(gi), mr_of(gi), P(g.gamma_off),
                             u->cfg.num_groups, B, D >> lv, H >> lv, W >> lv, dt, grd(x0), a0, grd(x1), a1,
-                            GR(g.gamma_p), GR(g.beta_p), gb + G.gnws, G.gnws_bytes, nullptr, 0, stream, 1,
-                            pre ? pre->part : nullptr, pre ? pre->nblk : 0);
-  };
+                            GR(g.gamma_p), GR(g.beta_p), gb + G.gnws, G.gnws_bytes, o.chs, o.chs_stride, stream, 1,
+                            pre.part, pre.nblk, o.coef_out, o.film);
+  }
+  // d(emb rows k) in deb -> the emb projection's gradients (and a folded-in conv bias's), d SiLU(time embedding)
+  int emb_bwd(int k) {
+    const int roff = u->emb_rows_off[k];
+    return launch_emb_bwd(deb + roff, u->R, u->emb_rows_n[k], (int)B, temb, u->E,
+                          P(u->off_emb_w) + (int64_t)roff * u->E, GR(u->emb_rows_w[k]), GR(u->emb_rows_b[k]),
+                          u->emb_rows_cb[k] >= 0 ? GR(u->emb_rows_cb[k]) : nullptr, dsil, s, 1);
+  }
 
-  for (int seg = seg_begin; seg < seg_end; ++seg) {
-    const int nb = (int)u->blocks.size();
-    if (seg == 0) {
-      u->ginit.assign(u->tensors.size(), 0);
-      CWDM_HIP(hipMemsetAsync(grads, 0, u->grad_numel * 4, s));
-      CWDM_HIP(hipMemsetAsync(deb, 0, B * (int64_t)u->R * 4, s));
-      CWDM_HIP(hipMemsetAsync(dsil, 0, B * (int64_t)u->E * 4, s));
-      // output head: dout -> padded compute-dtype buffer
-      const int oc = u->cfg.out_channels, ocp = ckpad(u, oc);
-      const int64_t V0 = D * H * W;
-      void* d16 = gb + G.dout;
-      CWDM_HIP(hipMemsetAsync(d16, 0, B * V0 * ocp * es, s));
-      const int64_t ss_[3] = {V0 * oc, 1, oc}, ds_[3] = {V0 * ocp, 1, ocp};
-      if ((rc = cwdm_copy3(dout, CWDM_F32, ss_, d16, dt, ds_, B, oc, V0, stream))) return rc;
-      const auto& co = u->convs[u->head_c];
-      const auto& hg = u->gns[u->head_g];
-      if ((rc = cwdm_channel_sum(d16, dt, B, V0, oc, ocp, nullptr, 0, GR(co.b_p), nullptr, gb + G.chs, G.chs_bytes,
-                                 stream)))
-        return rc;
-      if ((rc = wgrad(0, 3, act(co.a0), co.cin_a, nullptr, 0, 0, ss_of(u->head_g), d16, ocp, oc, GR(co.w_p))))
-        return rc;
-      Pre pre;
-      if ((rc = dgrad_gn(u->head_c, d16, u->head_g, hg.src0, -1, pre))) return rc;
-      if ((rc = gn_bwd(u->head_g, hg.src0, -1, 0, &pre))) return rc;
-      continue;
-    }
-    if (seg <= nb && u->blocks[nb - seg].updown == 8) {
-      // the bottleneck AttentionBlock: y = x + proj_out(attention(qkv(GroupNorm(x))))
-      const Block& bk = u->blocks[nb - seg];
-      const auto& at = u->attns[bk.pool];
-      const auto& g = u->gns[at.gn];
-      CWDM_REQUIRE(kept, CWDM_E_WORKSPACE,
-                   "cwdm_unet_backward: the attention block needs the forward's training workspace "
-                   "(cwdm_unet_train_workspace_bytes: it keeps the log-sum-exp rows and the normalised input)");
-      const int C = at.C, lv = at.level, o = at.out, xt = at.src;
-      const int64_t T = vox(lv);
-      const unsigned char* qkv = wb + L.attn_qkv;
-      unsigned char* dqkv = gb + G.at_dqkv;
-      void* da = gb + G.at_da;
-      void* dn = gb + G.at_dn;
-      // ---- proj_out: bias, weight, input gradient
-      if ((rc = cwdm_channel_sum(grd(o), dt, B, T, C, C, nullptr, 0, GR(at.proj_b_p), nullptr, gb + G.chs, G.chs_bytes,
-                                 stream)))
-        return rc;
-      if ((rc = wgrad(lv, 1, wb + L.attn_a, C, nullptr, 0, 0, nullptr, grd(o), C, C, GR(at.proj_w_p)))) return rc;
-      if ((rc = cwdm::attn_linear(dt, B, T, C, C, grd(o), nullptr, pb + at.projT_off, nullptr, nullptr, da, nullptr,
-                                  nullptr, s)))
-        return rc;
-      // ---- softmax(q k^T) v
-      cwdm_attention_desc ad{};
-      ad.dtype = dt; ad.B = B; ad.T = T; ad.heads = at.heads; ad.ch = at.ch;
-      ad.q = qkv; ad.k = qkv + (int64_t)C * es; ad.v = qkv + (int64_t)2 * C * es;
-      ad.q_rs = ad.k_rs = ad.v_rs = 3 * C; ad.q_bs = ad.k_bs = ad.v_bs = T * 3 * C;
-      ad.o = const_cast<unsigned char*>(wb + L.attn_a); ad.o_rs = C; ad.o_bs = T * C;
-      ad.L = const_cast<float*>(reinterpret_cast<const float*>(wb + L.attn_L));
-      ad.D = reinterpret_cast<float*>(gb + G.at_D);
-      ad.d_o = da; ad.do_rs = C; ad.do_bs = T * C;
-      ad.dq = dqkv; ad.dk = dqkv + (int64_t)C * es; ad.dv = dqkv + (int64_t)2 * C * es;
-      ad.dq_rs = ad.dk_rs = ad.dv_rs = 3 * C; ad.dq_bs = ad.dk_bs = ad.dv_bs = T * 3 * C;
-      if ((rc = cwdm_attention_backward(&ad, stream))) return rc;
-      // ---- qkv: bias, weight (rows back to the model's order), input gradient
-      const bool legacy = !u->cfg.attn_new_order;
-      float* dwp = legacy ? reinterpret_cast<float*>(gb + G.at_dw) : GR(at.qkv_w_p);
-      float* dbp = legacy ? dwp + (int64_t)3 * C * C : GR(at.qkv_b_p);
-      if (legacy) CWDM_HIP(hipMemsetAsync(dwp, 0, ((int64_t)3 * C * C + 3 * C) * 4, s));
-      if ((rc = cwdm_channel_sum(dqkv, dt, B, T, 3 * C, 3 * C, nullptr, 0, dbp, nullptr, gb + G.chs, G.chs_bytes,
-                                 stream)))
-        return rc;
-      if ((rc = wgrad(lv, 1, wb + L.attn_n, C, nullptr, 0, 0, nullptr, dqkv, 3 * C, 3 * C, dwp))) return rc;
-      if (legacy) {
-        if ((rc = cwdm::attn_unperm_add(dwp, GR(at.qkv_w_p), 3 * C, C, at.heads, at.ch, s))) return rc;
-        if ((rc = cwdm::attn_unperm_add(dbp, GR(at.qkv_b_p), 3 * C, 1, at.heads, at.ch, s))) return rc;
-      }
-      if ((rc = cwdm::attn_linear(dt, B, T, 3 * C, C, dqkv, nullptr, pb + at.qkvT_off, nullptr, nullptr, dn, nullptr,
-                                  nullptr, s)))
-        return rc;
-      // ---- the norm (no activation) and the residual: dx = dy + dGN(dn)
-      if ((rc = cwdm::gn_lin_bwd(dt, B, T, C, u->cfg.num_groups, act(xt), dn, mr_of(at.gn), P(g.gamma_off), grd(o),
-                                 grd(xt), take_acc(xt), reinterpret_cast<float*>(gb + G.at_part), GR(g.gamma_p),
-                                 GR(g.beta_p), s)))
-        return rc;
-      continue;
-    }
-    if (seg <= nb && u->blocks[nb - seg].updown == 7) {
-      // WavUNetModel WaveletDownsample (wunet.py:131-145): out = conv(cat(DWT(pyr)) / 3) + h
-      const Block& bk = u->blocks[nb - seg];
-      const auto& cs = u->convs[bk.c1];
-      const auto& hp = u->haars[bk.pool];
-      const int o = cs.out;
-      if ((rc = cwdm_channel_sum(grd(o), dt, B, vox(cs.level), cs.cout, cs.cout, nullptr, 0, GR(cs.b_p), nullptr,
-                                 gb + G.chs, G.chs_bytes, stream)))
-        return rc;
-      if ((rc = wgrad(cs.level, 3, act(hp.out), cs.cin_a, nullptr, 0, 0, nullptr, grd(o), cs.cout, cs.cout,
-                      GR(cs.w_p))))
-        return rc;
-      const int lv = cs.level;
-      if ((rc = cwdm_resample_add(grd(cs.res), grd(o), cs.cout, B, D >> lv, H >> lv, W >> lv, 0, take_acc(cs.res), dt,
-                                  stream)))
-        return rc;
-      if (hp.src != u->input_tensor) {   // the level-0 pyramid is the model input: no gradient
-        if ((rc = dgrad(bk.c1, grd(o)))) return rc;
-        const int cp = u->tensors[hp.src].channels;
-        if ((rc = haar_nd_synth_add(dt, B, D >> lv, H >> lv, W >> lv, cp, tmp, 8LL * cp, hp.lll_scale,
-                                    reinterpret_cast<unsigned char*>(tmp) + (int64_t)cp * es, 8LL * cp, hp.high_scale,
-                                    grd(hp.src), take_acc(hp.src), s)))
-          return rc;
-      }
-      continue;
-    }
-    if (seg <= nb && (u->blocks[nb - seg].updown == 5 || u->blocks[nb - seg].updown == 6)) {
-      // WavUNetModel ResBlock that resamples by DWT / IDWT after its first conv (wunet.py:210-269)
-      const Block& bk = u->blocks[nb - seg];
-      const bool down = bk.updown == 5;
-      const auto& c1 = u->convs[bk.c1];
-      const auto& c2 = u->convs[bk.c2];
-      const auto& hh = u->haars[bk.hh];
-      const auto& hx = u->haars[bk.hx];
-      const int lout = c2.level, lin = c1.level;
-      const int64_t Vo = vox(lout);
-      const int o = c2.out, h1 = c1.out, cout = c2.cout, cin = u->tensors[bk.x0].channels;
-      // ---- conv2 + the residual x_upd
-      if ((rc = cwdm_channel_sum(grd(o), dt, B, Vo, cout, cout, nullptr, 0, GR(c2.b_p), nullptr, gb + G.chs,
-                                 G.chs_bytes, stream)))
-        return rc;
-      if ((rc = wgrad_c(bk.c2, lout, act(hh.out), cout, nullptr, 0, 0, ss_of(bk.g2), grd(o), cout, cout,
-                        GR(c2.w_p))))
-        return rc;
-      if ((rc = cwdm_resample_add(grd(hx.out), grd(o), cout, B, D >> lout, H >> lout, W >> lout, 0, take_acc(hx.out),
-                                  dt, stream)))
-        return rc;
-      Pre pre2;
-      if ((rc = dgrad_gn(bk.c2, grd(o), bk.g2, hh.out, -1, pre2))) return rc;
-      // ---- GN2 -> d(h + emb), with its channel sums = the emb projection's gradient
-      const int k = bk.emb_k;
-      const int roff = u->emb_rows_off[k], rn = u->emb_rows_n[k];
-      {
-        const auto& g = u->gns[bk.g2];
-        if ((rc = gn_silu_bwd_impl(act(hh.out), cout, nullptr, 0, tmp, 0, ss_of(bk.g2), mr_of(bk.g2), P(g.gamma_off),
-                                   u->cfg.num_groups, B, D >> lout, H >> lout, W >> lout, dt, grd(hh.out),
-                                   take_acc(hh.out), nullptr, 0, GR(g.gamma_p), GR(g.beta_p), gb + G.gnws,
-                                   G.gnws_bytes, deb + roff, u->R, stream, 1, pre2.part, pre2.nblk)))
-          return rc;
-      }
-      if ((rc = launch_emb_bwd(deb + roff, u->R, rn, (int)B, temb, u->E, P(u->off_emb_w) + (int64_t)roff * u->E,
-                               GR(u->emb_rows_w[k]), GR(u->emb_rows_b[k]), nullptr, dsil, s, 1)))
-        return rc;
-      // ---- the resampling adjoints (orthonormal Haar: analysis <-> synthesis)
-      const int lc = down ? lout : lin;   // the coarse grid of this block's DWT / IDWT
-      const int64_t dc = D >> lc, hc = H >> lc, wc = W >> lc;
-      if (down) {
-        // h = DWT(h1): LLL / 3 (+ emb) continues, the 7 high bands are the skip
-        const int sk = hh.high_out;
-        const void* dsk = u->ginit[sk] ? grd(sk) : nullptr;   // (no later user: zero)
-        if ((rc = haar_nd_synth_add(dt, B, dc, hc, wc, cout, grd(hh.out), cout, hh.lll_scale, dsk, 7LL * cout,
-                                    hh.high_scale, grd(h1), take_acc(h1), s)))
-          return rc;
-        if ((rc = haar_nd_synth_add(dt, B, dc, hc, wc, cin, grd(hx.out), cin, hx.lll_scale, nullptr, 0, 0.f,
-                                    grd(bk.x0), take_acc(bk.x0), s)))
-          return rc;
-      } else {
-        // h = IDWT(3 h1, skip) (+ emb), x_upd = IDWT(3 x, skip): both feed the skip bands' gradient
-        const int sk = hh.high_in;
-        if ((rc = haar_nd_anal_add(dt, B, dc, hc, wc, cout, grd(hh.out), grd(h1), cout, hh.lll_scale, take_acc(h1),
-                                   grd(sk), 7LL * cout, hh.high_scale, take_acc(sk), s)))
-          return rc;
-        if ((rc = haar_nd_anal_add(dt, B, dc, hc, wc, cin, grd(hx.out), grd(bk.x0), cin, hx.lll_scale,
-                                   take_acc(bk.x0), grd(sk), 7LL * cin, hx.high_scale, take_acc(sk), s)))
-          return rc;
-      }
-      // ---- conv1 (own bias; the emb is added after the resampling) and GN1
-      if ((rc = cwdm_channel_sum(grd(h1), dt, B, vox(lin), cout, cout, nullptr, 0, GR(c1.b_p), nullptr, gb + G.chs,
-                                 G.chs_bytes, stream)))
-        return rc;
-      if ((rc = wgrad_c(bk.c1, lin, act(bk.x0), cin, nullptr, 0, 0, ss_of(bk.g1), grd(h1), cout, cout, GR(c1.w_p))))
-        return rc;
-      Pre pre1;
-      if ((rc = dgrad_gn(bk.c1, grd(h1), bk.g1, bk.x0, -1, pre1))) return rc;
-      if ((rc = gn_bwd(bk.g1, bk.x0, -1, 0, &pre1))) return rc;
-      continue;
-    }
-    if (seg <= nb && u->blocks[nb - seg].updown >= 3) {
-      // Downsample stride-2 conv / Upsample nearest + conv (resblock_updown=False)
-      const Block& bk = u->blocks[nb - seg];
-      const auto& cs = u->convs[bk.c1];
-      const int o = cs.out, xt = bk.x0;
-      const int chn = u->tensors[xt].channels, lx = u->tensors[xt].level;
-      if ((rc = cwdm_channel_sum(grd(o), dt, B, vox(cs.level), cs.cout, cs.cout, nullptr, 0, GR(cs.b_p), nullptr,
-                                 gb + G.chs, G.chs_bytes, stream)))
-        return rc;
-      if (bk.updown == 4) {
-        if ((rc = wgrad(cs.level, 3, act(xt), chn, nullptr, 0, 1, nullptr, grd(o), cs.cout, cs.cout, GR(cs.w_p))))
-          return rc;
-        if ((rc = dgrad(bk.c1, grd(o)))) return rc;
-        if ((rc = cwdm_resample_add(grd(xt), tmp, chn, B, D >> lx, H >> lx, W >> lx, 1, take_acc(xt), dt, stream)))
-          return rc;
-      } else {
-        const auto& sd = u->s2ds[bk.pool];
-        float* dwe = reinterpret_cast<float*>(gb + G.dwe);
-        CWDM_HIP(hipMemsetAsync(dwe, 0, (int64_t)cs.cout * cs.cin_a * 27 * 4, s));
-        if ((rc = wgrad(cs.level, 3, act(sd.out), cs.cin_a, nullptr, 0, 0, nullptr, grd(o), cs.cout, cs.cout, dwe)))
-          return rc;
-        if ((rc = cwdm_conv3d_s2_fold_dw(dwe, cs.cout, chn, GR(cs.w_p), 1, stream))) return rc;
-        if ((rc = dgrad(bk.c1, grd(o)))) return rc;
-        if ((rc = cwdm_space_to_depth(tmp, chn, B, D >> cs.level, H >> cs.level, W >> cs.level, dt, grd(xt), 0,
-                                      take_acc(xt), stream)))
-          return rc;
-      }
-      continue;
-    }
-    if (seg <= nb) {
-      const Block& bk = u->blocks[nb - seg];
-      const auto& c1 = u->convs[bk.c1];
-      const auto& c2 = u->convs[bk.c2];
-      const int lout = c2.level;
-      const int64_t Vo = vox(lout);
-      const int o = c2.out, h1 = c1.out;
-      const int cout = c2.cout;
-      // additive skips: the block's input is (h + skip) / 2; once its gradient is complete, the adjoint
-      // hands half of it to h and to the skip (whose encoder consumer runs later and accumulates)
-      auto avg_bwd = [&]() -> int {
-        if (bk.avg < 0) return CWDM_OK;
-        const auto& as = u->avgs[bk.avg];
-        const int aa = take_acc(as.a), ab = take_acc(as.b);
-        return cwdm_skip_avg_bwd(grd(as.out), grd(as.a), aa, grd(as.b), ab, dt, B, vox(as.level), as.channels,
-                                 stream);
-      };
-      // ---- conv2 (+ skip / residual)
-      if ((rc = cwdm_channel_sum(grd(o), dt, B, Vo, cout, cout, nullptr, 0, GR(c2.b_p),
-                                 c2.wsb_p >= 0 ? GR(c2.wsb_p) : nullptr, gb + G.chs, G.chs_bytes, stream)))
-        return rc;
-      if ((rc = wgrad_c(bk.c2, lout, act(h1), cout, nullptr, 0, 0, ss_of(bk.g2), grd(o), cout, cout, GR(c2.w_p))))
-        return rc;
-      // 1x1 skip dgrad into dx0 / dx1 (dual output); with skip_gapply the
-      // GroupNorm-1 backward's apply pass rides in its epilogue (GapplyFuse),
-      // so it runs after GN1's reduce / finalize below
-      auto skip_dgrad_desc = [&]() {
-        const int c0 = u->tensors[c2.sb0].channels, cc1 = c2.sb1 >= 0 ? u->tensors[c2.sb1].channels : 0;
-        cwdm_conv3d_desc d{};
-        d.dtype = dt; d.B = B; d.D = D >> lout; d.H = H >> lout; d.W = W >> lout;
-        d.cout = c0 + cc1;
-        d.b0 = grd(o); d.b_c0 = cout; d.b_w = pb + u->dgs_off[bk.c2];
-        d.res_mode = -1;
-        d.out = grd(c2.sb0); d.out_dtype = dt;
-        if (c2.sb1 >= 0) { d.out1 = grd(c2.sb1); d.out_c0 = c0; }
-        return d;
-      };
-      // (its route would take an offered apply)
-      auto skip_takes_gapply = [&]() {
-        const cwdm_conv3d_desc d = skip_dgrad_desc();
-        cwdm::GapplyFuse probe{};
-        cwdm::ConvCall cc;
-        cc.gapply = &probe;
-        return cwdm::conv_route(&d, cc).takes_gapply;
-      };
-      auto skip_dgrad = [&](cwdm::GapplyFuse* gf) -> int {
-        cwdm_conv3d_desc d = skip_dgrad_desc();
-        // equalise the store/accumulate state of the two outputs
-        int a0 = take_acc(c2.sb0), a1 = c2.sb1 >= 0 ? take_acc(c2.sb1) : a0;
-        if (a0 != a1) {
-          const int zid = a0 ? c2.sb1 : c2.sb0;
-          const auto& zt = u->tensors[zid];
-          CWDM_HIP(hipMemsetAsync(grd(zid), 0, B * vox(zt.level) * zt.channels * es, s));
-          a0 = a1 = 1;
-        }
-        d.accumulate = a0;
-        d.workspace = gb + G.split; d.ws_bytes = G.split_bytes;
-        cwdm::ConvCall cc;
-        cc.sync = sync;
-        cc.gapply = gf;
-        if (int r = cwdm::conv3d_forward(&d, cc, s)) return r;
-        CWDM_REQUIRE(!gf || gf->used, CWDM_E_UNSUPPORTED, "train plan: skip dgrad did not take the fused apply");
-        return CWDM_OK;
-      };
-      static const bool gapply_on = env_not0("CWDM_GAPPLY_FUSE");
-      const bool skip_gapply = c2.ws_p >= 0 && gapply_on && bk.updown == 0 && c2.sb0 == bk.x0 &&
-                               c2.sb1 == bk.x1 && skip_takes_gapply();
-      if (c2.ws_p >= 0) {
-        const int c0 = u->tensors[c2.sb0].channels, cc1 = c2.sb1 >= 0 ? u->tensors[c2.sb1].channels : 0;
-        if ((rc = wgrad(lout, 1, act(c2.sb0), c0, act(c2.sb1), cc1, 0, nullptr, grd(o), cout, cout, GR(c2.ws_p))))
-          return rc;
-        if (!skip_gapply && (rc = skip_dgrad(nullptr))) return rc;
-      } else {
-        // identity residual (possibly through the block's resampling)
-        const int xt = bk.x0;
-        const int lx = u->tensors[xt].level;
-        const int mode = bk.updown == 2 ? 2 : (bk.updown == 1 ? 1 : 0);
-        if ((rc = cwdm_resample_add(grd(xt), grd(o), cout, B, D >> lx, H >> lx, W >> lx, mode, take_acc(xt), dt,
-                                    stream)))
-          return rc;
-      }
-      Pre pre2;
-      if ((rc = dgrad_gn(bk.c2, grd(o), bk.g2, h1, -1, pre2))) return rc;
-      // ---- GN2 -> dh1, with the per-channel sums of dh1 (the emb projection's
-      // gradient) taken in the same pass when dh1 is written, not accumulated
-      const int k = bk.emb_k;
-      const int roff = u->emb_rows_off[k], rn = u->emb_rows_n[k];
-      const bool fuse_sum = !u->ginit[h1];
-      const bool film = u->gns[bk.g2].film_row >= 0;
-      if (film) {
-        // FiLM: the finalize writes d scale / d shift into the block's rows; conv1 has its own bias, whose
-        // gradient (the sum of dh1 over voxels and batch) is the apply pass's channel sums finished per channel
-        const auto& g = u->gns[bk.g2];
-        const float* ebias = reinterpret_cast<const float*>(wb + L.ebias);
-        cwdm::GnBwdFilm gf{P(g.beta_off), ebias + roff, u->R, deb + roff, u->R, fuse_sum ? GR(c1.b_p) : nullptr};
-        if ((rc = gn_silu_bwd_impl(act(h1), cout, nullptr, 0, tmp, 0, ss_of(bk.g2), mr_of(bk.g2), P(g.gamma_off),
-                                   u->cfg.num_groups, B, D >> lout, H >> lout, W >> lout, dt, grd(h1), take_acc(h1),
-                                   nullptr, 0, GR(g.gamma_p), GR(g.beta_p), gb + G.gnws, G.gnws_bytes, nullptr, 0,
-                                   stream, 1, pre2.part, pre2.nblk, nullptr, &gf)))
-          return rc;
-        if (!fuse_sum && (rc = cwdm_channel_sum(grd(h1), dt, B, Vo, cout, cout, nullptr, 0, GR(c1.b_p), nullptr,
-                                                gb + G.chs, G.chs_bytes, stream)))
-          return rc;
-      } else if (fuse_sum) {
-        const auto& g = u->gns[bk.g2];
-        if ((rc = gn_silu_bwd_impl(act(h1), cout, nullptr, 0, tmp, 0, ss_of(bk.g2), mr_of(bk.g2), P(g.gamma_off),
-                                   u->cfg.num_groups, B, D >> lout, H >> lout, W >> lout, dt, grd(h1), take_acc(h1),
-                                   nullptr, 0, GR(g.gamma_p), GR(g.beta_p), gb + G.gnws, G.gnws_bytes, deb + roff, u->R,
-                                   stream, 1, pre2.part, pre2.nblk)))
-          return rc;
-      } else {
-        if ((rc = gn_bwd(bk.g2, h1, -1, 0, &pre2))) return rc;
-        if ((rc = cwdm_channel_sum(grd(h1), dt, B, Vo, cout, cout, deb + roff, u->R, nullptr, nullptr, gb + G.chs,
-                                   G.chs_bytes, stream)))
-          return rc;
-      }
-      // ---- conv1: emb projection, wgrad, dgrad
-      if ((rc = launch_emb_bwd(deb + roff, u->R, rn, (int)B, temb, u->E, P(u->off_emb_w) + (int64_t)roff * u->E,
-                               GR(u->emb_rows_w[k]), GR(u->emb_rows_b[k]),
-                               u->emb_rows_cb[k] >= 0 ? GR(u->emb_rows_cb[k]) : nullptr, dsil, s, 1)))
-        return rc;
-      if (bk.updown == 2) {
-        const auto& ps = u->pools[bk.pool];
-        if ((rc = wgrad(lout, 3, act(ps.out_h), ps.channels, nullptr, 0, 0, nullptr, grd(h1), cout, cout,
-                        GR(c1.w_p))))
-          return rc;
-      } else {
-        const int c0 = u->tensors[bk.x0].channels, cc1 = bk.x1 >= 0 ? u->tensors[bk.x1].channels : 0;
-        if ((rc = wgrad_c(bk.c1, lout, act(bk.x0), c0, act(bk.x1), cc1, bk.updown == 1 ? 1 : 0, ss_of(bk.g1),
-                          grd(h1), cout, cout, GR(c1.w_p))))
-          return rc;
-      }
-      // ---- GN1 (+ resample adjoint) -> dx0 / dx1 (the reduce in the dgrad's epilogue
-      // when the GroupNorm's grid is the conv's: no resampling in between)
-      Pre pre1;
-      if (bk.updown == 0) {
-        if ((rc = dgrad_gn(bk.c1, grd(h1), bk.g1, bk.x0, bk.x1, pre1))) return rc;
-      } else if ((rc = dgrad(bk.c1, grd(h1)))) {
-        return rc;
-      }
-      if (skip_gapply) {
-        // GN1 reduce / finalize, then the skip dgrad applying it: dx = skip + GN1 backward
-        const auto& g = u->gns[bk.g1];
-        const int c0 = u->tensors[bk.x0].channels, cc1 = bk.x1 >= 0 ? u->tensors[bk.x1].channels : 0;
-        const float* coef = nullptr;
-        if ((rc = gn_silu_bwd_impl(act(bk.x0), c0, act(bk.x1), cc1, tmp, 0, ss_of(bk.g1), mr_of(bk.g1),
-                                   P(g.gamma_off), u->cfg.num_groups, B, D >> lout, H >> lout, W >> lout, dt,
-                                   grd(bk.x0), 0, grd(bk.x1), 0, GR(g.gamma_p), GR(g.beta_p), gb + G.gnws,
-                                   G.gnws_bytes, nullptr, 0, stream, 1, pre1.part, pre1.nblk, &coef)))
-          return rc;
-        cwdm::GapplyFuse gf{};
-        gf.x0 = act(bk.x0); gf.x1 = act(bk.x1); gf.du = tmp; gf.ss = ss_of(bk.g1); gf.coef = coef;
-        if ((rc = skip_dgrad(&gf))) return rc;
-        if ((rc = avg_bwd())) return rc;
-        continue;
-      }
-      if ((rc = gn_bwd(bk.g1, bk.x0, bk.x1, bk.updown == 1 ? 1 : (bk.updown == 2 ? 2 : 0), &pre1))) return rc;
-      if ((rc = avg_bwd())) return rc;
-      continue;
-    }
-    // conv_in + time_embed
-    const auto& c0 = u->convs[0];
+  // ---- segment 0: zero the gradients, then the output head (out.0 GroupNorm, out.2 conv)
+  int head() {
+    int rc;
+    u->ginit.assign(u->tensors.size(), 0);
+    CWDM_HIP(hipMemsetAsync(grads, 0, u->grad_numel * 4, s));
+    CWDM_HIP(hipMemsetAsync(deb, 0, B * (int64_t)u->R * 4, s));
+    CWDM_HIP(hipMemsetAsync(dsil, 0, B * (int64_t)u->E * 4, s));
+    // dout -> padded compute-dtype buffer
+    const int oc = u->cfg.out_channels, ocp = ckpad(u, oc);
     const int64_t V0 = D * H * W;
-    if ((rc = cwdm_channel_sum(grd(c0.out), dt, B, V0, c0.cout, c0.cout, nullptr, 0, GR(c0.b_p), nullptr, gb + G.chs,
-                               G.chs_bytes, stream)))
+    void* d16 = gb + G.dout;
+    CWDM_HIP(hipMemsetAsync(d16, 0, B * V0 * ocp * es, s));
+    const int64_t ss_[3] = {V0 * oc, 1, oc}, ds_[3] = {V0 * ocp, 1, ocp};
+    if ((rc = cwdm_copy3(dout, CWDM_F32, ss_, d16, dt, ds_, B, oc, V0, stream))) return rc;
+    const auto& co = u->convs[u->head_c];
+    const auto& hg = u->gns[u->head_g];
+    if ((rc = bias_grad(d16, 0, oc, GR(co.b_p), nullptr, ocp))) return rc;
+    if ((rc = wgrad(0, 3, act(co.a0), co.cin_a, nullptr, 0, 0, ss_of(u->head_g), d16, ocp, oc, GR(co.w_p))))
       return rc;
+    Pre pre;
+    if ((rc = dgrad_gn(u->head_c, d16, u->head_g, hg.src0, -1, pre))) return rc;
+    return gn_bwd(u->head_g, hg.src0, -1, 0, pre);
+  }
+
+  // ---- the bottleneck AttentionBlock: y = x + proj_out(attention(qkv(GroupNorm(x))))
+  int attention(const Block& bk) {
+    const auto& at = u->attns[bk.attn];
+    const auto& g = u->gns[at.gn];
+    CWDM_REQUIRE(kept, CWDM_E_WORKSPACE,
+                 "cwdm_unet_backward: the attention block needs the forward's training workspace "
+                 "(cwdm_unet_train_workspace_bytes: it keeps the log-sum-exp rows and the normalised input)");
+    const int C = at.C, lv = at.level, o = at.out, xt = at.src;
+    const int64_t T = vox(lv);
+    unsigned char* dqkv = gb + G.at_dqkv;
+    void *da = gb + G.at_da, *dn = gb + G.at_dn;
+    int rc;
+    // ---- proj_out: bias, weight, input gradient
+    if ((rc = bias_grad(grd(o), lv, C, GR(at.proj_b_p)))) return rc;
+    if ((rc = wgrad(lv, 1, wb + L.attn_a, C, nullptr, 0, 0, nullptr, grd(o), C, C, GR(at.proj_w_p)))) return rc;
+    if ((rc = cwdm::attn_linear(dt, B, T, C, C, grd(o), nullptr, pb + at.projT_off, nullptr, nullptr, da, nullptr,
+                                nullptr, s)))
+      return rc;
+    // ---- softmax(q k^T) v
+    cwdm_attention_desc ad = attn_desc(at, dt, B, T, wb + L.attn_qkv, const_cast<unsigned char*>(wb + L.attn_a),
+                                       const_cast<float*>(reinterpret_cast<const float*>(wb + L.attn_L)));
+    ad.D = reinterpret_cast<float*>(gb + G.at_D);
+    ad.d_o = da; ad.do_rs = C; ad.do_bs = T * C;
+    ad.dq = dqkv; ad.dk = dqkv + (int64_t)C * es; ad.dv = dqkv + (int64_t)2 * C * es;
+    ad.dq_rs = ad.dk_rs = ad.dv_rs = 3 * C; ad.dq_bs = ad.dk_bs = ad.dv_bs = T * 3 * C;
+    if ((rc = cwdm_attention_backward(&ad, stream))) return rc;
+    // ---- qkv: bias, weight (rows back to the model's order), input gradient
+    const bool legacy = !u->cfg.attn_new_order;
+    float* dwp = legacy ? reinterpret_cast<float*>(gb + G.at_dw) : GR(at.qkv_w_p);
+    float* dbp = legacy ? dwp + (int64_t)3 * C * C : GR(at.qkv_b_p);
+    if (legacy) CWDM_HIP(hipMemsetAsync(dwp, 0, ((int64_t)3 * C * C + 3 * C) * 4, s));
+    if ((rc = bias_grad(dqkv, lv, 3 * C, dbp))) return rc;
+    if ((rc = wgrad(lv, 1, wb + L.attn_n, C, nullptr, 0, 0, nullptr, dqkv, 3 * C, 3 * C, dwp))) return rc;
+    if (legacy) {
+      if ((rc = cwdm::attn_unperm_add(dwp, GR(at.qkv_w_p), 3 * C, C, at.heads, at.ch, s))) return rc;
+      if ((rc = cwdm::attn_unperm_add(dbp, GR(at.qkv_b_p), 3 * C, 1, at.heads, at.ch, s))) return rc;
+    }
+    if ((rc = cwdm::attn_linear(dt, B, T, 3 * C, C, dqkv, nullptr, pb + at.qkvT_off, nullptr, nullptr, dn, nullptr,
+                                nullptr, s)))
+      return rc;
+    // ---- the norm (no activation) and the residual: dx = dy + dGN(dn)
+    return cwdm::gn_lin_bwd(dt, B, T, C, u->cfg.num_groups, act(xt), dn, mr_of(at.gn), P(g.gamma_off), grd(o),
+                            grd(xt), take_acc(xt), reinterpret_cast<float*>(gb + G.at_part), GR(g.gamma_p),
+                            GR(g.beta_p), s);
+  }
+
+  // ---- WavUNetModel WaveletDownsample (wunet.py:131-145): out = conv(cat(DWT(pyr)) / 3) + h
+  int wav_pyramid(const Block& bk) {
+    const auto& cs = u->convs[bk.c1];
+    const auto& hp = u->haars[bk.haar];
+    const int o = cs.out, lv = cs.level;
+    int rc;
+    if ((rc = bias_grad(grd(o), lv, cs.cout, GR(cs.b_p)))) return rc;
+    if ((rc = wgrad(lv, 3, act(hp.out), cs.cin_a, nullptr, 0, 0, nullptr, grd(o), cs.cout, cs.cout, GR(cs.w_p))))
+      return rc;
+    if ((rc = resample_add(cs.res, grd(o), cs.cout, lv, 0))) return rc;
+    if (hp.src == u->input_tensor) return CWDM_OK;   // the level-0 pyramid is the model input: no gradient
+    if ((rc = dgrad(bk.c1, grd(o)))) return rc;
+    const int cp = u->tensors[hp.src].channels;
+    return haar_nd_synth_add(dt, B, D >> lv, H >> lv, W >> lv, cp, tmp, 8LL * cp, hp.lll_scale,
+                             reinterpret_cast<unsigned char*>(tmp) + (int64_t)cp * es, 8LL * cp, hp.high_scale,
+                             grd(hp.src), take_acc(hp.src), s);
+  }
+
+  // ---- WavUNetModel ResBlock that resamples by DWT / IDWT after its first conv (wunet.py:210-269)
+  int wav_resblock(const Block& bk) {
+    const bool down = bk.kind == BlockKind::WavDown;
+    const auto& c1 = u->convs[bk.c1];
+    const auto& c2 = u->convs[bk.c2];
+    const auto& hh = u->haars[bk.hh];
+    const auto& hx = u->haars[bk.hx];
+    const int lout = c2.level, lin = c1.level, o = c2.out, h1 = c1.out, cout = c2.cout, cin = nch(bk.x0);
+    int rc;
+    // ---- conv2 + the residual x_upd
+    if ((rc = bias_grad(grd(o), lout, cout, GR(c2.b_p)))) return rc;
+    if ((rc = wgrad_c(bk.c2, lout, act(hh.out), cout, nullptr, 0, 0, ss_of(bk.g2), grd(o), cout, cout, GR(c2.w_p))))
+      return rc;
+    if ((rc = resample_add(hx.out, grd(o), cout, lout, 0))) return rc;
+    Pre pre2;
+    if ((rc = dgrad_gn(bk.c2, grd(o), bk.g2, hh.out, -1, pre2))) return rc;
+    // ---- GN2 -> d(h + emb), with its channel sums = the emb projection's gradient
+    const GnBwdOpt g2{deb + u->emb_rows_off[bk.emb_k], u->R};
+    if ((rc = gn_bwd(bk.g2, hh.out, -1, 0, pre2, g2))) return rc;
+    if ((rc = emb_bwd(bk.emb_k))) return rc;
+    // ---- the resampling adjoints (orthonormal Haar: analysis <-> synthesis)
+    const int lc = down ? lout : lin;   // the coarse grid of this block's DWT / IDWT
+    const int64_t dc = D >> lc, hc = H >> lc, wc = W >> lc;
+    if (down) {
+      // h = DWT(h1): LLL / 3 (+ emb) continues, the 7 high bands are the skip
+      const int sk = hh.high_out;
+      const void* dsk = u->ginit[sk] ? grd(sk) : nullptr;   // (no later user: zero)
+      if ((rc = haar_nd_synth_add(dt, B, dc, hc, wc, cout, grd(hh.out), cout, hh.lll_scale, dsk, 7LL * cout,
+                                  hh.high_scale, grd(h1), take_acc(h1), s)))
+        return rc;
+      if ((rc = haar_nd_synth_add(dt, B, dc, hc, wc, cin, grd(hx.out), cin, hx.lll_scale, nullptr, 0, 0.f,
+                                  grd(bk.x0), take_acc(bk.x0), s)))
+        return rc;
+    } else {
+      // h = IDWT(3 h1, skip) (+ emb), x_upd = IDWT(3 x, skip): both feed the skip bands' gradient
+      const int sk = hh.high_in;
+      const int a_h1 = take_acc(h1), a_sk = take_acc(sk);
+      if ((rc = haar_nd_anal_add(dt, B, dc, hc, wc, cout, grd(hh.out), grd(h1), cout, hh.lll_scale, a_h1, grd(sk),
+                                 7LL * cout, hh.high_scale, a_sk, s)))
+        return rc;
+      const int a_x0 = take_acc(bk.x0), a_sk2 = take_acc(sk);
+      if ((rc = haar_nd_anal_add(dt, B, dc, hc, wc, cin, grd(hx.out), grd(bk.x0), cin, hx.lll_scale, a_x0, grd(sk),
+                                 7LL * cin, hx.high_scale, a_sk2, s)))
+        return rc;
+    }
+    // ---- conv1 (own bias; the emb is added after the resampling) and GN1
+    if ((rc = bias_grad(grd(h1), lin, cout, GR(c1.b_p)))) return rc;
+    if ((rc = wgrad_c(bk.c1, lin, act(bk.x0), cin, nullptr, 0, 0, ss_of(bk.g1), grd(h1), cout, cout, GR(c1.w_p))))
+      return rc;
+    Pre pre1;
+    if ((rc = dgrad_gn(bk.c1, grd(h1), bk.g1, bk.x0, -1, pre1))) return rc;
+    return gn_bwd(bk.g1, bk.x0, -1, 0, pre1);
+  }
+
+  // ---- Downsample stride-2 conv / Upsample nearest + conv (resblock_updown=False)
+  int resample_layer(const Block& bk) {
+    const auto& cs = u->convs[bk.c1];
+    const int o = cs.out, xt = bk.x0, lv = cs.level;
+    const int chn = u->tensors[xt].channels, lx = u->tensors[xt].level;
+    int rc;
+    if ((rc = bias_grad(grd(o), lv, cs.cout, GR(cs.b_p)))) return rc;
+    if (bk.kind == BlockKind::Upsample) {
+      if ((rc = wgrad(lv, 3, act(xt), chn, nullptr, 0, 1, nullptr, grd(o), cs.cout, cs.cout, GR(cs.w_p)))) return rc;
+      if ((rc = dgrad(bk.c1, grd(o)))) return rc;
+      return resample_add(xt, tmp, chn, lx, 1);
+    }
+    const auto& sd = u->s2ds[bk.s2d];
+    float* dwe = reinterpret_cast<float*>(gb + G.dwe);
+    CWDM_HIP(hipMemsetAsync(dwe, 0, (int64_t)cs.cout * cs.cin_a * 27 * 4, s));
+    if ((rc = wgrad(lv, 3, act(sd.out), cs.cin_a, nullptr, 0, 0, nullptr, grd(o), cs.cout, cs.cout, dwe))) return rc;
+    if ((rc = cwdm_conv3d_s2_fold_dw(dwe, cs.cout, chn, GR(cs.w_p), 1, stream))) return rc;
+    if ((rc = dgrad(bk.c1, grd(o)))) return rc;
+    return cwdm_space_to_depth(tmp, chn, B, D >> lv, H >> lv, W >> lv, dt, grd(xt), 0, take_acc(xt), stream);
+  }
+
+  // ---- ResBlock (Res / ResUp / ResDown), in the stages of the comment above
+  // 1x1 skip dgrad into dx0 / dx1 (dual output)
+  cwdm_conv3d_desc skip_dgrad_desc(const Block& bk) const {
+    const auto& c2 = u->convs[bk.c2];
+    cwdm_conv3d_desc d{};
+    d.dtype = dt; d.B = B; d.D = D >> c2.level; d.H = H >> c2.level; d.W = W >> c2.level;
+    d.cout = nch(c2.sb0) + nch(c2.sb1); d.res_mode = -1;
+    d.b0 = grd(c2.out); d.b_c0 = c2.cout; d.b_w = pb + u->dgs_off[bk.c2];
+    d.out = grd(c2.sb0); d.out_dtype = dt;
+    if (c2.sb1 >= 0) { d.out1 = grd(c2.sb1); d.out_c0 = nch(c2.sb0); }
+    return d;
+  }
+  // (its route would take an offered apply)
+  bool skip_takes_gapply(const Block& bk) const {
+    const cwdm_conv3d_desc d = skip_dgrad_desc(bk);
+    cwdm::GapplyFuse probe{};
+    cwdm::ConvCall cc;
+    cc.gapply = &probe;
+    return cwdm::conv_route(&d, cc).takes_gapply;
+  }
+  int skip_dgrad(const Block& bk, cwdm::GapplyFuse* gf) {
+    const auto& c2 = u->convs[bk.c2];
+    cwdm_conv3d_desc d = skip_dgrad_desc(bk);
+    // equalise the store/accumulate state of the two outputs
+    int a0 = take_acc(c2.sb0), a1 = c2.sb1 >= 0 ? take_acc(c2.sb1) : a0;
+    if (a0 != a1) {
+      const int zid = a0 ? c2.sb1 : c2.sb0;
+      const auto& zt = u->tensors[zid];
+      CWDM_HIP(hipMemsetAsync(grd(zid), 0, B * vox(zt.level) * zt.channels * es, s));
+      a0 = a1 = 1;
+    }
+    d.accumulate = a0;
+    d.workspace = gb + G.split; d.ws_bytes = G.split_bytes;
+    cwdm::ConvCall cc;
+    cc.sync = sync; cc.gapply = gf;
+    if (int r = cwdm::conv3d_forward(&d, cc, s)) return r;
+    CWDM_REQUIRE(!gf || gf->used, CWDM_E_UNSUPPORTED, "train plan: skip dgrad did not take the fused apply");
+    return CWDM_OK;
+  }
+  // additive skips: the block's input is (h + skip) / 2; once its gradient is complete, the adjoint
+  // hands half of it to h and to the skip (whose encoder consumer runs later and accumulates)
+  int avg_bwd(const Block& bk) {
+    if (bk.avg < 0) return CWDM_OK;
+    const auto& as = u->avgs[bk.avg];
+    const int aa = take_acc(as.a), ab = take_acc(as.b);
+    return cwdm_skip_avg_bwd(grd(as.out), grd(as.a), aa, grd(as.b), ab, dt, B, vox(as.level), as.channels, stream);
+  }
+  // GN2 -> dh1, with the per-channel sums of dh1 (the emb projection's
+  // gradient) taken in the same pass when dh1 is written, not accumulated
+  int resblock_gn2(const Block& bk, const Pre& pre2) {
+    const auto& c1 = u->convs[bk.c1];
+    const auto& g = u->gns[bk.g2];
+    const int h1 = c1.out, cout = c1.cout, roff = u->emb_rows_off[bk.emb_k];
+    const bool fuse_sum = !u->ginit[h1], film = g.film_row >= 0;
+    // FiLM: the finalize writes d scale / d shift into the block's rows; conv1 has its own bias, whose
+    // gradient (the sum of dh1 over voxels and batch) is the apply pass's channel sums finished per channel
+    const float* ebias = reinterpret_cast<const float*>(wb + L.ebias);
+    const cwdm::GnBwdFilm gf{P(g.beta_off), ebias + roff, u->R, deb + roff, u->R, fuse_sum ? GR(c1.b_p) : nullptr};
+    GnBwdOpt o;
+    if (film) o.film = &gf;
+    else if (fuse_sum) { o.chs = deb + roff; o.chs_stride = u->R; }
+    if (int rc = gn_bwd(bk.g2, h1, -1, 0, pre2, o)) return rc;
+    if (fuse_sum) return CWDM_OK;
+    // dh1 was accumulated: its sums (conv1's bias gradient / the emb rows') in a pass of their own
+    if (film) return bias_grad(grd(h1), c1.level, cout, GR(c1.b_p));
+    return cwdm_channel_sum(grd(h1), dt, B, vox(c1.level), cout, cout, deb + roff, u->R, nullptr, nullptr,
+                            gb + G.chs, G.chs_bytes, stream);
+  }
+  int resblock(const Block& bk) {
+    const auto& c1 = u->convs[bk.c1];
+    const auto& c2 = u->convs[bk.c2];
+    const int lout = c2.level, o = c2.out, h1 = c1.out, cout = c2.cout, mode = resample_mode(bk.kind);
+    int rc;
+    // ---- conv2 (+ skip / residual)
+    if ((rc = bias_grad(grd(o), lout, cout, GR(c2.b_p), c2.wsb_p >= 0 ? GR(c2.wsb_p) : nullptr))) return rc;
+    if ((rc = wgrad_c(bk.c2, lout, act(h1), cout, nullptr, 0, 0, ss_of(bk.g2), grd(o), cout, cout, GR(c2.w_p))))
+      return rc;
+    // with skip_gapply the GroupNorm-1 backward's apply pass rides in the skip dgrad's epilogue
+    // (GapplyFuse), so that conv runs after GN1's reduce / finalize below
+    static const bool gapply_on = env_not0("CWDM_GAPPLY_FUSE");
+    const bool skip_gapply = c2.ws_p >= 0 && gapply_on && bk.kind == BlockKind::Res && c2.sb0 == bk.x0 &&
+                             c2.sb1 == bk.x1 && skip_takes_gapply(bk);
+    if (c2.ws_p >= 0) {
+      if ((rc = wgrad(lout, 1, act(c2.sb0), nch(c2.sb0), act(c2.sb1), nch(c2.sb1), 0, nullptr, grd(o), cout, cout,
+                      GR(c2.ws_p))))
+        return rc;
+      if (!skip_gapply && (rc = skip_dgrad(bk, nullptr))) return rc;
+    } else {
+      // identity residual (possibly through the block's resampling)
+      if ((rc = resample_add(bk.x0, grd(o), cout, u->tensors[bk.x0].level, mode))) return rc;
+    }
+    Pre pre2;
+    if ((rc = dgrad_gn(bk.c2, grd(o), bk.g2, h1, -1, pre2))) return rc;
+    if ((rc = resblock_gn2(bk, pre2))) return rc;
+    // ---- conv1: emb projection, wgrad, dgrad
+    if ((rc = emb_bwd(bk.emb_k))) return rc;
+    if (bk.kind == BlockKind::ResDown) {
+      const auto& ps = u->pools[bk.pool];
+      if ((rc = wgrad(lout, 3, act(ps.out_h), ps.channels, nullptr, 0, 0, nullptr, grd(h1), cout, cout, GR(c1.w_p))))
+        return rc;
+    } else if ((rc = wgrad_c(bk.c1, lout, act(bk.x0), nch(bk.x0), act(bk.x1), nch(bk.x1), mode, ss_of(bk.g1), grd(h1),
+                             cout, cout, GR(c1.w_p)))) {
+      return rc;
+    }
+    // ---- GN1 (+ resample adjoint) -> dx0 / dx1 (the reduce in the dgrad's epilogue
+    // when the GroupNorm's grid is the conv's: no resampling in between)
+    Pre pre1;
+    rc = bk.kind == BlockKind::Res ? dgrad_gn(bk.c1, grd(h1), bk.g1, bk.x0, bk.x1, pre1) : dgrad(bk.c1, grd(h1));
+    if (rc) return rc;
+    if (skip_gapply) {
+      // GN1 reduce / finalize, then the skip dgrad applying it: dx = skip + GN1 backward
+      const float* coef = nullptr;
+      GnBwdOpt g1;
+      g1.coef_out = &coef; g1.keep_acc = true;
+      if ((rc = gn_bwd(bk.g1, bk.x0, bk.x1, 0, pre1, g1))) return rc;
+      cwdm::GapplyFuse gf{};
+      gf.x0 = act(bk.x0); gf.x1 = act(bk.x1); gf.du = tmp; gf.ss = ss_of(bk.g1); gf.coef = coef;
+      if ((rc = skip_dgrad(bk, &gf))) return rc;
+    } else if ((rc = gn_bwd(bk.g1, bk.x0, bk.x1, mode, pre1))) {
+      return rc;
+    }
+    return avg_bwd(bk);
+  }
+
+  // ---- the last segment: conv_in + time_embed
+  int stem() {
+    const auto& c0 = u->convs[0];
+    int rc;
+    if ((rc = bias_grad(grd(c0.out), 0, c0.cout, GR(c0.b_p)))) return rc;
     if ((rc = wgrad(0, 3, x, c0.cin_a, nullptr, 0, 0, nullptr, grd(c0.out), c0.cout, c0.cout, GR(c0.w_p)))) return rc;
-    if ((rc = launch_temb_bwd(t, (int)B, u->cfg.model_channels, P(u->off_te_w1), P(u->off_te_b1), P(u->off_te_w2),
-                              temb, dsil, GR(u->te_w1), GR(u->te_b1), GR(u->te_w2), GR(u->te_b2), s)))
-      return rc;
+    return launch_temb_bwd(t, (int)B, u->cfg.model_channels, P(u->off_te_w1), P(u->off_te_b1), P(u->off_te_w2), temb,
+                           dsil, GR(u->te_w1), GR(u->te_b1), GR(u->te_w2), GR(u->te_b2), s);
+  }
+};
+
+}  // namespace
+
+extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* packed_bwd, const void* x,
+                                  const float* t, const float* dout, float* grads, int64_t B, int64_t D, int64_t H,
+                                  int64_t W, const void* ws, int64_t ws_bytes, void* gws, int64_t gws_bytes,
+                                  int seg_begin, int seg_end, cwdm_stream_t stream) {
+  CWDM_REQUIRE(u && packed && packed_bwd && x && t && dout && grads && ws && gws, CWDM_E_INVALID,
+               "cwdm_unet_backward: null pointer");
+  const int nb = (int)u->blocks.size(), nseg = nb + 2;
+  CWDM_REQUIRE(0 <= seg_begin && seg_begin <= seg_end && seg_end <= nseg, CWDM_E_INVALID,
+               "cwdm_unet_backward: bad segment range");
+  CWDM_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, CWDM_E_SHAPE, "cwdm_unet_backward: empty grid");
+  const int64_t div = int64_t(1) << (u->cfg.num_levels - (u->cfg.use_freq ? 0 : 1));
+  CWDM_REQUIRE(D % div == 0 && H % div == 0 && W % div == 0, CWDM_E_SHAPE,
+               "cwdm_unet_backward: every subband edge must be divisible by " + std::to_string(div));
+  const Layout L = layout(u, B, D, H, W);
+  const GLayout G = glayout(u, B, D, H, W);
+  CWDM_REQUIRE(ws_bytes >= L.total, CWDM_E_WORKSPACE, "cwdm_unet_backward: forward workspace too small");
+  CWDM_REQUIRE(gws_bytes >= G.total, CWDM_E_WORKSPACE,
+               "cwdm_unet_backward: grad workspace too small (need " + std::to_string(G.total) + " bytes)");
+  CWDM_REQUIRE(seg_begin == 0 || (int)u->ginit.size() == (int)u->tensors.size(), CWDM_E_INVALID,
+               "cwdm_unet_backward: segment 0 must run first");
+  using UC = unsigned char;
+  Backward bw{u, L, G, reinterpret_cast<const UC*>(packed), reinterpret_cast<const UC*>(packed_bwd),
+              reinterpret_cast<const UC*>(ws), reinterpret_cast<UC*>(gws), x, t, dout, grads, B, D, H, W,
+              L.train_total > L.total && ws_bytes >= L.train_total, stream};
+  // (every call: a caller may run segments on a fresh grad workspace)
+  CWDM_HIP(hipMemsetAsync(bw.sync, 0, cwdm::plan_sync_bytes(), bw.s));
+  // segment 0 the output head, then the blocks last to first, then conv_in + time_embed
+  for (int seg = seg_begin; seg < seg_end; ++seg) {
+    int rc = CWDM_OK;
+    if (seg == 0) rc = bw.head();
+    else if (seg > nb) rc = bw.stem();
+    else switch (const Block& bk = u->blocks[nb - seg]; bk.kind) {
+      case BlockKind::Attention: rc = bw.attention(bk); break;
+      case BlockKind::WavPyramid: rc = bw.wav_pyramid(bk); break;
+      case BlockKind::WavDown:
+      case BlockKind::WavUp: rc = bw.wav_resblock(bk); break;
+      case BlockKind::Downsample:
+      case BlockKind::Upsample: rc = bw.resample_layer(bk); break;
+      case BlockKind::Res:
+      case BlockKind::ResUp:
+      case BlockKind::ResDown: rc = bw.resblock(bk); break;
+    }
+    if (rc) return rc;
   }
   return CWDM_OK;
 }
