@@ -567,6 +567,40 @@ extern "C" int cwdm_debug_conv_route(const cwdm_conv3d_desc* d, int* out, int n)
   return CWDM_OK;
 }
 
+// tests: a dgrad conv offered the fused GroupNorm-backward reduce as the U-Net plan's dgrad_gn offers it
+// (unet_plan.cpp: a GbwdFuse in the call's context); used / nblk as the call left them
+extern "C" int cwdm_debug_conv3d_gbwd(const cwdm_conv3d_desc* d, const void* x0, const void* x1, int c0,
+                                      const float* scale_shift, const float* mean_rstd, int groups, float* part,
+                                      int64_t part_bytes, int* used, int* nblk, cwdm_stream_t stream) {
+  CWDM_REQUIRE(d && x0 && scale_shift && mean_rstd && part && used && nblk, CWDM_E_INVALID,
+               "cwdm_debug_conv3d_gbwd: null pointer");
+  GbwdFuse f{};
+  f.x0 = x0; f.x1 = x1; f.c0 = c0;
+  f.ss = scale_shift; f.mr = mean_rstd; f.groups = groups; f.part = part;
+  f.part_bytes = part_bytes;
+  ConvCall cc;
+  cc.gbwd = &f;
+  const int rc = conv3d_forward(d, cc, (hipStream_t)stream);
+  *used = f.used ? 1 : 0;
+  *nblk = f.nblk;
+  return rc;
+}
+
+// tests: a 1x1 skip dgrad offered the fused GroupNorm-backward apply as the plan's skip_dgrad offers it
+extern "C" int cwdm_debug_conv3d_gapply(const cwdm_conv3d_desc* d, const void* x0, const void* x1, const void* du,
+                                        const float* scale_shift, const float* coef, int* used,
+                                        cwdm_stream_t stream) {
+  CWDM_REQUIRE(d && x0 && du && scale_shift && coef && used && (!d->out1 || x1), CWDM_E_INVALID,
+               "cwdm_debug_conv3d_gapply: null pointer");
+  GapplyFuse gf{};
+  gf.x0 = x0; gf.x1 = x1; gf.du = du; gf.ss = scale_shift; gf.coef = coef;
+  ConvCall cc;
+  cc.gapply = &gf;
+  const int rc = conv3d_forward(d, cc, (hipStream_t)stream);
+  *used = gf.used ? 1 : 0;
+  return rc;
+}
+
 // the brick / split-K kernels of conv3d_kernels.hpp (every shape and mode)
 int cwdm::legacy_conv3d_forward(const cwdm_conv3d_desc* d, ProfHook* prof, hipStream_t s) {
   const Plan1 pl = plan_conv(d);

@@ -901,6 +901,27 @@ extern "C" int cwdm_gn_silu_bwd_film(const void* x0, int c0, const void* x1, int
                           dgamma, dbeta, ws, ws_bytes, nullptr, 0, stream, 0, nullptr, 0, nullptr, &f);
 }
 
+// tests: gn_silu_bwd_impl with the arguments only the U-Net plan passes (unet_plan.cpp gn_bwd)
+extern "C" int cwdm_debug_gn_silu_bwd_ex(const void* x0, int c0, const void* x1, int c1, const void* du, int du_mode,
+                                         const float* ss, const float* mr, const float* gamma, int groups, int64_t B,
+                                         int64_t d, int64_t h, int64_t w, int dtype, void* dx0, int acc0, void* dx1,
+                                         int acc1, float* dgamma, float* dbeta, void* ws, int64_t ws_bytes,
+                                         float* chs, int64_t chs_stride, int acc_affine, const float* pre_part,
+                                         int pre_nblk, int coef_mode, const float** coef, cwdm_stream_t stream) {
+  CWDM_REQUIRE(!coef_mode || coef, CWDM_E_INVALID, "cwdm_debug_gn_silu_bwd_ex: coef_mode without a place for the pointer");
+  return gn_silu_bwd_impl(x0, c0, x1, c1, du, du_mode, ss, mr, gamma, groups, B, d, h, w, dtype, dx0, acc0, dx1, acc1,
+                          dgamma, dbeta, ws, ws_bytes, chs, chs_stride, stream, acc_affine, pre_part, pre_nblk,
+                          coef_mode ? coef : nullptr);
+}
+
+// tests: gb_part_reduce; in == NULL: the slice count the plan uses (kGbSlices), nothing launched
+extern "C" int cwdm_debug_gb_part_reduce(const float* in, int nblk, int C, int64_t B, int slices, float* out,
+                                         cwdm_stream_t stream) {
+  if (!in) return kGbSlices;
+  CWDM_REQUIRE(out && C > 0, CWDM_E_INVALID, "cwdm_debug_gb_part_reduce: null pointer");
+  return gb_part_reduce(in, nblk, C, B, slices, out, (hipStream_t)stream);
+}
+
 extern "C" int cwdm_resample_add(void* dst, const void* src, int C, int64_t B, int64_t d, int64_t h, int64_t w,
                                  int mode, int accumulate, int dtype, cwdm_stream_t stream) {
   CWDM_REQUIRE(dst && src, CWDM_E_INVALID, "cwdm_resample_add: null pointer");

@@ -173,6 +173,7 @@ int gn_silu_bwd_impl(const void* x0, int c0, const void* x1, int c1, const void*
                      const float* pre_part = nullptr, int pre_nblk = 0, const float** coef_out = nullptr,
                      const GnBwdFilm* film = nullptr);
 int gb_part_reduce(const float* part, int nblk, int C, int64_t B, int slices, float* out, hipStream_t s);
+constexpr int kGbSlices = 64;   // slice sums the plan takes of the fused GroupNorm-backward partials (gb_part_reduce)
 // attention.hip: the bottleneck attention block's projections (cwdm_attn_linear / cwdm_attn_pack with
 // their arguments spelled out), the adjoint of the legacy row permutation for the qkv gradients
 // (dst[source row][c] += src[packed row][c]), and the backward of a GroupNorm without activation:

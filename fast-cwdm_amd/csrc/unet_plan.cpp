@@ -1588,8 +1588,6 @@ struct GLayout {
   int64_t total;
 };
 
-constexpr int kGbSlices = 64;   // slice sums of the fused GroupNorm-backward partials (cwdm::gb_part_reduce)
-
 int ckpad(const cwdm_unet* u, int c) {
   const int ck = ck_of(u->cfg.dtype);
   return (c + ck - 1) / ck * ck;

@@ -210,6 +210,15 @@ _PROTOS = {
     "cwdm_gn_silu_bwd_film": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp,
                                              ctypes.c_int, i64, i64, i64, i64, ctypes.c_int, vp, ctypes.c_int, vp,
                                              ctypes.c_int, vp, vp, vp, i64, vp, vp, i64, vp, i64, vp]),
+    "cwdm_debug_conv3d_gbwd": (ctypes.c_int, [ctypes.POINTER(ConvDesc), vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp,
+                                              i64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), vp]),
+    "cwdm_debug_conv3d_gapply": (ctypes.c_int, [ctypes.POINTER(ConvDesc), vp, vp, vp, vp, vp,
+                                                ctypes.POINTER(ctypes.c_int), vp]),
+    "cwdm_debug_gn_silu_bwd_ex": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp,
+                                                 ctypes.c_int, i64, i64, i64, i64, ctypes.c_int, vp, ctypes.c_int, vp,
+                                                 ctypes.c_int, vp, vp, vp, i64, vp, i64, ctypes.c_int, vp,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp), vp]),
+    "cwdm_debug_gb_part_reduce": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, i64, ctypes.c_int, vp, vp]),
     "cwdm_resample_add": (ctypes.c_int, [vp, vp, ctypes.c_int, i64, i64, i64, i64, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, vp]),
     "cwdm_channel_sum_workspace_bytes": (i64, [i64, i64, ctypes.c_int]),

@@ -648,6 +648,55 @@ int cwdm_gn_silu_bwd_film(const void* x0, int c0, const void* x1, int c1, const 
                           void* workspace, int64_t ws_bytes, const float* beta, const float* film,
                           int64_t film_bstride, float* dfilm, int64_t dfilm_bstride, cwdm_stream_t stream);
 
+/* Tests only: the two backward fusions that only the U-Net plan's 16-bit
+ * training path reaches, with their context filled as the plan fills it (no
+ * kernel or rule of their own).
+ *
+ * cwdm_debug_conv3d_gbwd: cwdm_conv3d_forward(d) of a 3x3x3 dgrad conv (output
+ * du, d->cout = C channels) offered the reduce pass of the SiLU(GroupNorm)
+ * backward that consumes du: x0 (c0 channels) / x1 (C - c0, or NULL) = the
+ * GroupNorm's input at the conv's grid, scale_shift / mean_rstd / groups its
+ * forward statistics.  Where the conv takes the offer (*used = 1: 16-bit
+ * DMA-staged kernel without K split, W <= 32, C / groups >= 2, c0 a multiple of
+ * the kernel's 32- or 64-channel tile, part_bytes >= B * nblk * C * 8) its
+ * epilogue writes part [B][*nblk][C][2] = per 32x4x4 tile (x fastest) the sums
+ * over the tile's voxels of (dz, dz * xhat), dz = du SiLU'(x scale + shift), du
+ * as stored; else *used = 0, the conv runs as usual and part is not written.
+ *
+ * cwdm_debug_conv3d_gapply: cwdm_conv3d_forward(d) of a pure 1x1 conv (segment
+ * B; the skip dgrad, d->cout = N channels into out / out1) offered the apply
+ * pass of that backward: out (+)= conv + k0 SiLU'(x scale + shift) du + k1 x +
+ * k2, with x0 / x1 split as out / out1, du [B][V][N], coef [B][N][4] = (k0, k1,
+ * k2, -) as cwdm_debug_gn_silu_bwd_ex hands them out.  *used = 1 where the
+ * pointwise kernel took it (no bias, >= 256 voxels, channel splits in 8s).
+ *
+ * cwdm_debug_gn_silu_bwd_ex: cwdm_gn_silu_bwd plus the plan's arguments: chs /
+ * chs_stride (one source only: the per-channel sums of the written dx0 are
+ * ADDED to chs[b * chs_stride + c]), acc_affine (1: dgamma / dbeta are added to),
+ * pre_part / pre_nblk (the reduce pass is skipped; partials [B][pre_nblk][C][2]
+ * as cwdm_debug_conv3d_gbwd or cwdm_debug_gb_part_reduce wrote them; du_mode 0
+ * only), coef_mode (1: reduce + finalize only -- dx0 / dx1 are not touched --
+ * and *coef points at the [B][C][4] coefficients inside workspace).
+ *
+ * cwdm_debug_gb_part_reduce: fixed-order slice sums of partial rows, in
+ * [B][nblk][2 C] -> out [B][slices][2 C] (slice s = rows [s per, (s + 1) per),
+ * per = ceil(nblk / slices); slices past the last row are zero).  in == NULL:
+ * launches nothing and returns the slice count the plan uses. */
+int cwdm_debug_conv3d_gbwd(const cwdm_conv3d_desc* d, const void* x0, const void* x1, int c0,
+                           const float* scale_shift, const float* mean_rstd, int groups, float* part,
+                           int64_t part_bytes, int* used, int* nblk, cwdm_stream_t stream);
+int cwdm_debug_conv3d_gapply(const cwdm_conv3d_desc* d, const void* x0, const void* x1, const void* du,
+                             const float* scale_shift, const float* coef, int* used, cwdm_stream_t stream);
+int cwdm_debug_gn_silu_bwd_ex(const void* x0, int c0, const void* x1, int c1, const void* du, int du_mode,
+                              const float* scale_shift, const float* mean_rstd, const float* gamma, int groups,
+                              int64_t B, int64_t d, int64_t h, int64_t w, int dtype,
+                              void* dx0, int acc0, void* dx1, int acc1, float* dgamma, float* dbeta,
+                              void* workspace, int64_t ws_bytes, float* chs, int64_t chs_stride, int acc_affine,
+                              const float* pre_part, int pre_nblk, int coef_mode, const float** coef,
+                              cwdm_stream_t stream);
+int cwdm_debug_gb_part_reduce(const float* in, int nblk, int C, int64_t B, int slices, float* out,
+                              cwdm_stream_t stream);
+
 /* Adjoint of the resampling of a residual path: dst (grid d,h,w, C channels,
  * NDHWC, dtype) (+)= R^T src with mode 0 identity, 1 = src at the 2x grid
  * (adjoint of nearest-x2: sum of the 8 children), 2 = src at the half grid
