@@ -33,6 +33,8 @@ struct Tensor {
   int stats_kind = 0;  // producer of its (sum, sum^2) parts: 0 conv epilogue, 1 / 2 cwdm_haar_nd over its own /
                        // the half grid (analysis / synthesis output), 3 cwdm_skip_avg, 4 cwdm_attn_linear (one row
                        // per 16 voxels), -1 none (never GroupNorm'd)
+  bool grad = true;    // the backward keeps a gradient buffer for it (false: a dropout step's output, whose
+                       // gradient only passes through the scratch tmp)
 };
 
 struct GnStep {
@@ -89,6 +91,12 @@ struct HaarStep {  // WavUNetModel resampling / input pyramid (cwdm_haar_nd, wav
   int level;                        // the coarse grid's level
 };
 
+// dropout of a ResBlock's out_layers (cwdm_gn_silu_dropout, dropout.hip): out = mask * SiLU(GN(src)) / (1 - p),
+// the norm's scale / shift from buffer ss_id; site = the block's ordinal among the plan's ResBlocks
+struct DropStep {
+  int src, ss_id, out, level, channels, site;
+};
+
 struct AvgStep {  // additive skip (cwdm_skip_avg, skip_avg.hip): out = (a + b) / 2
   int a, b, out, level, channels;
 };
@@ -103,7 +111,7 @@ struct AttnStep {
 };
 
 enum StepKind { kGn, kConv, kPool /* pre-pass */, kS2d /* space-to-depth */, kHaar, kAvg /* additive skip */,
-                kAttn /* bottleneck attention */ };
+                kAttn /* bottleneck attention */, kDrop /* out_layers dropout */ };
 struct Step { StepKind kind; int idx; };
 
 // what one Block is: the backward runs one function per kind (struct Backward)
@@ -129,6 +137,8 @@ struct Block {
   BlockKind kind = BlockKind::Res;
   int g1 = -1, c1 = -1, g2 = -1, c2 = -1;  // u->gns / u->convs
   int pool = -1;                           // u->pools (ResDown)
+  int drop = -1;                           // u->drops (Res / ResUp / ResDown of a plan with dropout): conv2 reads
+                                           // its output, already activated, instead of h1 through g2
   int s2d = -1;                            // u->s2ds (Downsample)
   int haar = -1;                           // u->haars (WavPyramid)
   int attn = -1;                           // u->attns (Attention)
@@ -168,6 +178,8 @@ struct cwdm_unet {
   std::vector<HaarStep> haars;
   std::vector<AvgStep> avgs;
   std::vector<AttnStep> attns;
+  std::vector<DropStep> drops;
+  uint64_t dropout_seed = 0;      // cwdm_unet_set_dropout_seed: read when a dropout step or its backward is launched
   std::vector<Step> steps;
   struct Alias { std::string name; int owner, before; };
   std::vector<Alias> aliases;     // WavUNetModel: second state_dict name of a reused parameter; before = the
@@ -392,9 +404,22 @@ void build(cwdm_unet* u) {
     int g2 = gn_step(p + ".out_layers.0", h1, -1, lout);
     blk.g2 = g2;
     u->gns[g2].film_row = film_row;
+    int a2 = h1, gn2 = g2;
+    if (c.dropout > 0.0) {
+      // Dropout(p) between out_layers' SiLU and its conv (unet.py:255-262): the finalize runs on its own, one
+      // pass writes u = mask * SiLU(GN(h1)) / (1 - p), and conv2 reads u with no prologue (as conv1 reads a
+      // ResDown block's pooled input)
+      DropStep ds{h1, g2, new_tensor(lout, cout), lout, cout, (int)u->drops.size()};
+      u->tensors[ds.out].stats_kind = -1;
+      u->tensors[ds.out].grad = false;
+      u->drops.push_back(ds);
+      u->steps.push_back({kDrop, ds.site});
+      blk.drop = ds.site;
+      a2 = ds.out; gn2 = -1;
+    }
     ConvStep c2{};
     conv_params(p + ".out_layers.3", cout, cout, 3, &c2.w_p, &c2.b_p);
-    c2.a0 = h1; c2.a1 = -1; c2.amode = 0; c2.gn = g2; c2.cin_a = cout;
+    c2.a0 = a2; c2.a1 = -1; c2.amode = 0; c2.gn = gn2; c2.cin_a = cout;
     c2.sb0 = c2.sb1 = -1; c2.ws_p = c2.wsb_p = -1; c2.cin_b = 0;
     c2.res = -1; c2.rmode = -1;
     if (cin != cout) {
@@ -983,6 +1008,10 @@ extern "C" int cwdm_unet_create(const cwdm_unet_config* cfg, cwdm_unet** plan) {
                "cwdm_unet_create: additive_skips with use_freq (WavUNetModel has no concatenation to replace)");
   CWDM_REQUIRE(!(cfg->use_scale_shift_norm && cfg->use_freq), CWDM_E_UNSUPPORTED,
                "cwdm_unet_create: use_scale_shift_norm with use_freq (WavUNetModel's ResBlocks are not covered)");
+  CWDM_REQUIRE(cfg->dropout >= 0.0 && cfg->dropout < 1.0, CWDM_E_INVALID,
+               "cwdm_unet_create: dropout must lie in [0, 1)");
+  CWDM_REQUIRE(!(cfg->dropout > 0.0 && cfg->use_freq), CWDM_E_UNSUPPORTED,
+               "cwdm_unet_create: dropout with use_freq (WavUNetModel's ResBlocks are not covered)");
   if (cfg->bottleneck_attention) {
     CWDM_REQUIRE(!cfg->use_freq, CWDM_E_UNSUPPORTED,
                  "cwdm_unet_create: bottleneck_attention with use_freq (WavUNetModel's middle block is not covered)");
@@ -1031,6 +1060,12 @@ extern "C" void cwdm_unet_destroy(cwdm_unet* u) {
   (void)hipFree(u->bwd_tab);
   (void)hipFree(u->copy_tab);
   delete u;
+}
+
+extern "C" int cwdm_unet_set_dropout_seed(cwdm_unet* u, uint64_t seed) {
+  CWDM_REQUIRE(u, CWDM_E_INVALID, "cwdm_unet_set_dropout_seed: null plan");
+  u->dropout_seed = seed;
+  return CWDM_OK;
 }
 
 extern "C" int cwdm_unet_num_params(const cwdm_unet* u) { return u ? (int)u->params.size() : -1; }
@@ -1328,6 +1363,16 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
       if ((rc = cwdm_haar_nd(&a, stream))) return rc;
       continue;
     }
+    if (st.kind == kDrop) {
+      // (the norm's finalize ran just above: no conv takes it)
+      const auto& ds = u->drops[st.idx];
+      const int lv = ds.level;
+      if ((rc = cwdm_gn_silu_dropout(tptr(ds.src), reinterpret_cast<const float*>(wb + L.ss_off[ds.ss_id]),
+                                     wb + L.t_off[ds.out], u->cfg.dtype, B, (D >> lv) * (H >> lv) * (W >> lv),
+                                     ds.channels, u->cfg.dropout, u->dropout_seed, ds.site, stream)))
+        return rc;
+      continue;
+    }
     if (st.kind == kAvg) {
       const auto& as = u->avgs[st.idx];
       const int lv = as.level;
@@ -1566,7 +1611,8 @@ extern "C" int cwdm_unet_profile_read(cwdm_unet* u, double* ms, double* flops, i
 // (guided_diffusion/train_util.py:396-462).  Per ResBlock, in reverse:
 //   conv2: bias grad (channel sums), wgrad (input = SiLU(GN2(h1)) recomputed
 //          in the staging), skip 1x1 wgrad + dgrad or residual adjoint,
-//          dgrad (flipped/transposed weights, same implicit-GEMM kernel)
+//          dgrad (flipped/transposed weights, same implicit-GEMM kernel);
+//          with dropout the wgrad reads the stored u, and cwdm_dropout_bwd masks the dgrad's output
 //   GN2:   SiLU/GroupNorm backward -> dh1
 //   conv1: emb-projection grads (per-batch channel sums), wgrad, dgrad
 //   GN1:   SiLU/GroupNorm backward with the up/down resample adjoint -> dx
@@ -1616,7 +1662,7 @@ GLayout glayout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) 
   G.sync = take(cwdm::plan_sync_bytes());
   for (size_t i = 0; i < u->tensors.size(); ++i) {
     const auto& t = u->tensors[i];
-    if ((int)i == u->input_tensor) { G.g_off.push_back(-1); continue; }
+    if ((int)i == u->input_tensor || !t.grad) { G.g_off.push_back(-1); continue; }
     G.g_off.push_back(take(B * (D >> t.level) * (H >> t.level) * (W >> t.level) * t.channels * es));
   }
   int64_t tmp = 0, split = 0, gnws = 0, wgws = 0;
@@ -2118,8 +2164,11 @@ struct Backward {
     int rc;
     // ---- conv2 (+ skip / residual)
     if ((rc = bias_grad(grd(o), lout, cout, GR(c2.b_p), c2.wsb_p >= 0 ? GR(c2.wsb_p) : nullptr))) return rc;
-    if ((rc = wgrad_c(bk.c2, lout, act(h1), cout, nullptr, 0, 0, ss_of(bk.g2), grd(o), cout, cout, GR(c2.w_p))))
-      return rc;
+    // (a dropout block's conv2 read u = the dropout step's output, activated and masked already)
+    const DropStep* ds = bk.drop >= 0 ? &u->drops[bk.drop] : nullptr;
+    if (ds) rc = wgrad(lout, 3, act(ds->out), cout, nullptr, 0, 0, nullptr, grd(o), cout, cout, GR(c2.w_p));
+    else rc = wgrad_c(bk.c2, lout, act(h1), cout, nullptr, 0, 0, ss_of(bk.g2), grd(o), cout, cout, GR(c2.w_p));
+    if (rc) return rc;
     // with skip_gapply the GroupNorm-1 backward's apply pass rides in the skip dgrad's epilogue
     // (GapplyFuse), so that conv runs after GN1's reduce / finalize below
     static const bool gapply_on = env_not0("CWDM_GAPPLY_FUSE");
@@ -2135,7 +2184,15 @@ struct Backward {
       if ((rc = resample_add(bk.x0, grd(o), cout, u->tensors[bk.x0].level, mode))) return rc;
     }
     Pre pre2;
-    if ((rc = dgrad_gn(bk.c2, grd(o), bk.g2, h1, -1, pre2))) return rc;
+    if (ds) {
+      // du = conv2's plain input gradient, masked and scaled in place by the regenerated mask; the GroupNorm
+      // backward then takes its own reduce pass (a dgrad epilogue's partials would be of the unmasked gradient)
+      if ((rc = dgrad(bk.c2, grd(o)))) return rc;
+      if ((rc = cwdm_dropout_bwd(tmp, dt, B, vox(lout), cout, u->cfg.dropout, u->dropout_seed, ds->site, stream)))
+        return rc;
+    } else if ((rc = dgrad_gn(bk.c2, grd(o), bk.g2, h1, -1, pre2))) {
+      return rc;
+    }
     if ((rc = resblock_gn2(bk, pre2))) return rc;
     // ---- conv1: emb projection, wgrad, dgrad
     if ((rc = emb_bwd(bk.emb_k))) return rc;

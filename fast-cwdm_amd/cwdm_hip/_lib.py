@@ -97,6 +97,7 @@ class UNetConfig(ctypes.Structure):
         ("bottleneck_attention", ctypes.c_int), ("num_heads", ctypes.c_int),
         ("num_head_channels", ctypes.c_int), ("attn_new_order", ctypes.c_int),
         ("use_scale_shift_norm", ctypes.c_int),
+        ("dropout", ctypes.c_double),
     ]
 
 
@@ -184,6 +185,10 @@ _PROTOS = {
     "cwdm_gn_finalize_film": (ctypes.c_int, [vp, i64, ctypes.c_int, vp, i64, ctypes.c_int, vp, vp, ctypes.c_int, i64,
                                              i64, ctypes.c_float, vp, vp, vp, i64, vp]),
     "cwdm_gn_silu_pool": (ctypes.c_int, [vp, ctypes.c_int, vp, i64, i64, i64, i64, ctypes.c_int, vp, vp, vp]),
+    "cwdm_gn_silu_dropout": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, i64, i64, ctypes.c_int, ctypes.c_double,
+                                            ctypes.c_uint64, ctypes.c_int, vp]),
+    "cwdm_dropout_bwd": (ctypes.c_int, [vp, ctypes.c_int, i64, i64, ctypes.c_int, ctypes.c_double, ctypes.c_uint64,
+                                        ctypes.c_int, vp]),
     "cwdm_gn_apply": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, i64, i64, ctypes.c_int, vp, vp]),
     "cwdm_conv3d_set_path": (ctypes.c_int, [ctypes.c_int]),
     "cwdm_debug_v5_grid": (ctypes.c_int, [ctypes.c_int]),
@@ -231,6 +236,7 @@ _PROTOS = {
     "cwdm_adamw_maxabs": (ctypes.c_int, [vp, vp, vp, vp, i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                          ctypes.c_double, ctypes.c_double, i64, vp, vp]),
     "cwdm_unet_create": (ctypes.c_int, [ctypes.POINTER(UNetConfig), ctypes.POINTER(vp)]),
+    "cwdm_unet_set_dropout_seed": (ctypes.c_int, [vp, ctypes.c_uint64]),
     "cwdm_unet_destroy": (None, [vp]),
     "cwdm_unet_num_params": (ctypes.c_int, [vp]),
     "cwdm_unet_num_aliases": (ctypes.c_int, [vp]),

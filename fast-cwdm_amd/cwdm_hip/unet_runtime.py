@@ -32,7 +32,7 @@ class UNetPlan:
     def __init__(self, in_channels, model_channels, out_channels, num_res_blocks, channel_mult, num_groups,
                  dtype="fp32", resblock_updown=True, use_freq=False, additive_skips=False,
                  bottleneck_attention=False, num_heads=1, num_head_channels=-1, use_new_attention_order=False,
-                 use_scale_shift_norm=False):
+                 use_scale_shift_norm=False, dropout=0.0):
         cfg = _lib.UNetConfig()
         cfg.in_channels, cfg.model_channels, cfg.out_channels = in_channels, model_channels, out_channels
         cfg.num_res_blocks, cfg.num_levels = num_res_blocks, len(channel_mult)
@@ -51,6 +51,9 @@ class UNetPlan:
         cfg.num_head_channels = int(num_head_channels)
         cfg.attn_new_order = 1 if use_new_attention_order else 0
         cfg.use_scale_shift_norm = 1 if use_scale_shift_norm else 0
+        # > 0: a training plan whose every forward drops (cwdm_unet_config.dropout); set_dropout_seed names the masks
+        cfg.dropout = float(dropout)
+        self.dropout = float(dropout)
         self.use_freq = bool(use_freq)
         self.dtype = cfg.dtype
         self.torch_dtype = TORCH_DT[cfg.dtype]
@@ -107,6 +110,11 @@ class UNetPlan:
             arr = self.pointer_array(params)
         check(lib().cwdm_unet_pack(self._h, arr, ctypes.c_void_p(packed.data_ptr()), _stream()), "pack")
         return packed
+
+    def set_dropout_seed(self, seed):
+        """The 64-bit seed the plan's dropout masks are drawn with (host state, read at launch): set before a
+        forward and again before its backward."""
+        check(lib().cwdm_unet_set_dropout_seed(self._h, int(seed)))
 
     def workspace_bytes(self, B, D, H, W):
         n = int(lib().cwdm_unet_workspace_bytes(self._h, B, D, H, W))

@@ -27,6 +27,19 @@ multiple of 16, at most 256): GroupNorm + qkv projection, a streaming MFMA
 softmax(QK^T)V and proj_out + residual, three launches.
 ``attention_resolutions`` must stay empty.  Anything else raises
 NotImplementedError.
+
+``dropout=p`` (0 <= p < 1, else ValueError) is the reference's nn.Dropout(p)
+between every ResBlock's out_layers SiLU and its conv, and nowhere else; no
+parameters, so state_dicts are those of p = 0.  It is active iff
+``self.training and p > 0`` in ``forward`` (the nn.Module call), with or
+without grad: the model then runs a second plan whose ResBlocks carry one
+``cwdm_gn_silu_dropout`` pass, and the backward regenerates the same Philox
+mask (``cwdm_dropout_bwd``); nothing is stored.  One 64-bit
+seed per training forward comes from torch's CPU generator
+(``torch.manual_seed`` makes runs repeatable; ``model.dropout_seed = n``
+overrides the draw, ``model.last_dropout_seed`` is the one used).  The sampling
+seams ``forward_ndhwc`` / ``forward_step_ndhwc`` never drop, and ``eval()``
+gives bit for bit the forward of a ``dropout=0`` model with the same weights.
 """
 import math
 import os
@@ -82,6 +95,8 @@ class UNetModel(nn.Module):
         compute_dtype=None,
     ):
         super().__init__()
+        if not 0 <= dropout < 1:
+            raise ValueError(f"dropout must lie in [0, 1), got {dropout!r}")
         unsupported = []
         if dims != 3:
             unsupported.append(f"dims={dims} (3D only)")
@@ -93,8 +108,6 @@ class UNetModel(nn.Module):
             unsupported.append("resample_2d=True")
         if num_classes is not None:
             unsupported.append("class conditioning")
-        if dropout:
-            unsupported.append("dropout > 0")
         if unsupported:
             raise NotImplementedError("fast-cwdm_amd UNetModel covers the run.sh configuration only; unsupported: "
                                       + ", ".join(unsupported))
@@ -136,6 +149,10 @@ class UNetModel(nn.Module):
         if compute_dtype is None:
             compute_dtype = os.environ.get("CWDM_COMPUTE_DTYPE", "fp32")
         self.compute_dtype = compute_dtype
+        # dropout > 0: the seed of the next training forward's masks (None: drawn from torch's CPU generator,
+        # as the sampling loop draws its noise seed: no device sync), and the seed the last one used
+        self.dropout_seed = None
+        self.last_dropout_seed = None
         self._plans = {}
         spec_plan = self._plan(compute_dtype)
         # state_dict order; a reused block's second names (WavUNetModel) alias the owner's Parameter
@@ -246,8 +263,11 @@ class UNetModel(nn.Module):
                     bound = 1.0 / math.sqrt(w[0].numel())
                     p.uniform_(-bound, bound)
 
-    def _plan(self, dtype):
-        key = str(dtype)
+    def _plan(self, dtype, drop=False):
+        """The plan of a compute dtype; drop: the training plan of a model with dropout > 0, whose every
+        forward drops.  Both have the same parameters and the same packed layouts (the dropout step adds no
+        parameter and changes no conv's shape), so they share packed_weights() / packed_bwd_weights()."""
+        key = str(dtype) + ("+dropout" if drop else "")
         if key not in self._plans:
             self._plans[key] = UNetPlan(self.in_channels, self.model_channels, self.out_channels,
                                         self.num_res_blocks, self.channel_mult, self.num_groups, dtype,
@@ -256,8 +276,20 @@ class UNetModel(nn.Module):
                                         bottleneck_attention=bool(self.bottleneck_attention),
                                         num_heads=self.num_heads, num_head_channels=self.num_head_channels,
                                         use_new_attention_order=self.use_new_attention_order,
-                                        use_scale_shift_norm=self.use_scale_shift_norm)
+                                        use_scale_shift_norm=self.use_scale_shift_norm,
+                                        dropout=self.dropout if drop else 0.0)
         return self._plans[key]
+
+    def _drops(self):
+        """nn.Dropout's rule: active iff the module is in training mode (and p > 0), with or without grad."""
+        return self.training and self.dropout > 0
+
+    def _draw_dropout_seed(self):
+        seed = self.dropout_seed
+        if seed is None:
+            seed = int(th.randint(0, 2 ** 62, (1,)).item())
+        self.last_dropout_seed = int(seed)
+        return self.last_dropout_seed
 
     @property
     def plan(self):
@@ -346,7 +378,9 @@ class UNetModel(nn.Module):
     # ---- forward ------------------------------------------------------------
     def forward_ndhwc(self, x_ndhwc, t_f32, out_ndhwc):
         """Fast seam: x (B, D, H, W, in) in the compute dtype, t fp32[B] (model
-        timesteps), out (B, D, H, W, out) fp32; all device tensors."""
+        timesteps), out (B, D, H, W, out) fp32; all device tensors.  A sampling
+        seam: it never drops, whatever ``dropout`` and the training flag are (only
+        ``forward``, the nn.Module call, applies dropout)."""
         B, D, H, W, C = x_ndhwc.shape
         assert C == self.in_channels
         return self.plan.forward(self.packed_weights(), x_ndhwc, t_f32, out_ndhwc, B, D, H, W)
@@ -354,7 +388,8 @@ class UNetModel(nn.Module):
     def forward_step_ndhwc(self, x_ndhwc, t_f32, step):
         """forward_ndhwc followed by the sampling step ``step`` (ops.sampler_args,
         model_out = the (B, D, H, W, out) fp32 buffer), fused into the output
-        head when it qualifies; returns whether it was fused."""
+        head when it qualifies; returns whether it was fused.  Never drops (see
+        forward_ndhwc): the native p_sample_loop and the graph loop run through here."""
         B, D, H, W, C = x_ndhwc.shape
         assert C == self.in_channels
         return self.plan.forward_step(self.packed_weights(), x_ndhwc, t_f32, step, B, D, H, W)
@@ -381,7 +416,13 @@ class UNetModel(nn.Module):
             return _UNetTrain.apply(self, x, timesteps, *params)
         xin, t = self._prep_inputs(x, timesteps)
         out_nd = th.empty((B, D, H, W, self.out_channels), dtype=th.float32, device=x.device)
-        self.forward_ndhwc(xin, t, out_nd)
+        if self._drops():
+            # train() under no_grad drops too, as nn.Dropout does
+            plan = self._plan(self.compute_dtype, drop=True)
+            plan.set_dropout_seed(self._draw_dropout_seed())
+            plan.forward(self.packed_weights(), xin, t, out_nd, B, D, H, W)
+        else:
+            self.forward_ndhwc(xin, t, out_nd)
         return self._to_ncdhw(out_nd)
 
     def _prep_inputs(self, x, timesteps):
@@ -414,7 +455,14 @@ class _UNetTrain(th.autograd.Function):
     def forward(ctx, model, x, timesteps, *params):
         ctx.anchored = len(params) == 1 and params[0] is model.__dict__.get("_grad_anchor")
         B, C, D, H, W = x.shape
-        plan = model.plan
+        # dropout: the training plan, and this call's seed, handed to the plan before the forward and again
+        # before the backward (host state read at launch), so forwards and backwards may interleave
+        drop = model._drops()
+        plan = model._plan(model.compute_dtype, drop=drop)
+        ctx.plan = plan
+        ctx.drop_seed = model._draw_dropout_seed() if drop else None
+        if drop:
+            plan.set_dropout_seed(ctx.drop_seed)
         xin, t = model._prep_inputs(x, timesteps)
         # the training workspace: the forward keeps each DMA-staged conv's
         # activated input there for the backward's weight gradients
@@ -433,7 +481,7 @@ class _UNetTrain(th.autograd.Function):
         model = ctx.model
         xin, t, ws, (B, D, H, W) = ctx.state
         ctx.state = None
-        plan = model.plan
+        plan = ctx.plan
         oc = model.out_channels
         V = D * H * W
         dout = th.empty((B, D, H, W, oc), dtype=th.float32, device=xin.device)
@@ -444,9 +492,13 @@ class _UNetTrain(th.autograd.Function):
         hook = model._grad_hook
         nseg = plan.num_segments
         if hook is None:
+            if ctx.drop_seed is not None:
+                plan.set_dropout_seed(ctx.drop_seed)
             plan.backward(packed, packed_bwd, xin, t, dout, grads, B, D, H, W, ws, gws, 0, nseg)
         else:
             for seg in range(nseg):
+                if ctx.drop_seed is not None:
+                    plan.set_dropout_seed(ctx.drop_seed)
                 plan.backward(packed, packed_bwd, xin, t, dout, grads, B, D, H, W, ws, gws, seg, seg + 1)
                 off, n = plan.segment_range(seg)
                 hook(seg, grads, off, n)

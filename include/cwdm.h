@@ -467,6 +467,24 @@ int cwdm_gn_finalize_film(const float* stats0, int64_t parts0, int c0,
 int cwdm_gn_silu_pool(const void* x, int C, const float* gn, int64_t B, int64_t d, int64_t h, int64_t w,
                       int dtype, void* out_h, void* out_x, cwdm_stream_t stream);
 
+/* Dropout of a ResBlock's out_layers (nn.Dropout(p) between out_layers' SiLU and its conv,
+ * guided_diffusion/unet.py ResBlock), training only.  x, out, du: channels-last (B, V, C) in dtype, 16-byte
+ * aligned; scale_shift: [B][C][2] as for cwdm_conv3d_desc.a_gn.  The keep mask is never stored; both calls
+ * regenerate it from Philox4x32-10 (the sampler's generator), one block per 4 channels:
+ *   blk  = philox4x32_10(ctr = (v & 0xffffffff, v >> 32, site, (b << 16) | (c >> 2)),
+ *                        key = (seed & 0xffffffff, seed >> 32))
+ *   keep = (blk[c & 3] >> 8) >= floor(p * 2^24)
+ * with v the voxel index inside batch entry b, c the channel, site the caller's ordinal of the layer.  So
+ * the mask depends on neither the dtype, the values nor B.
+ *   cwdm_gn_silu_dropout: out = keep ? SiLU(x * scale + shift) * inv : 0, inv = 1.0f / (1.0f - (float)p);
+ *                         the product in fp32, rounded once to dtype
+ *   cwdm_dropout_bwd:     du  = keep ? du * inv : 0 in place (a select: a dropped Inf / NaN becomes 0)
+ * 0 <= p < 1 (else CWDM_E_INVALID); B < 65536 and C % 8 == 0 (else CWDM_E_UNSUPPORTED). */
+int cwdm_gn_silu_dropout(const void* x, const float* scale_shift, void* out, int dtype, int64_t B, int64_t V, int C,
+                         double p, uint64_t seed, int site, cwdm_stream_t stream);
+int cwdm_dropout_bwd(void* du, int dtype, int64_t B, int64_t V, int C, double p, uint64_t seed, int site,
+                     cwdm_stream_t stream);
+
 /* Conv kernel-path policy for cwdm_conv3d_forward (process-wide): 0 = auto
  * (DMA-staged kernels on wide grids with >= 512 tiles -- the warp-specialised
  * kernel with GroupNorm+SiLU in LDS where it applies, conv3d_v5.hip -- brick /
@@ -745,7 +763,9 @@ int cwdm_adamw_device_step(float* p, const float* g, float* m, float* v, int64_t
  * cwdm_attention_forward between cwdm_attn_linear's two projections; the
  * embedding added to conv1's output or, with use_scale_shift_norm, applied as
  * FiLM after out_layers.0: cwdm_gn_finalize_film folds it into the norm's
- * scale / shift table, no launch added).
+ * scale / shift table, no launch added; with dropout > 0, a training plan:
+ * one cwdm_gn_silu_dropout pass per ResBlock between out_layers.0 and
+ * out_layers.3, its mask regenerated by cwdm_dropout_bwd in the backward).
  * Topology and parameter names/shapes follow UNetModel.__init__
  * (unet.py:482-725) so reference state_dicts load unchanged.
  * ------------------------------------------------------------------------- */
@@ -777,9 +797,20 @@ typedef struct {
                                scale, shift = chunk(emb_out, 2) instead of adding emb_out to conv1's output
                                (unet.py ResBlock._forward); emb_layers.1 becomes Linear(E, 2 C_out).  Not with
                                use_freq.  0 (and a zeroed struct): off */
+  double dropout;           /* p of the nn.Dropout in every ResBlock's out_layers (unet.py:255-262), 0 <= p < 1.
+                               > 0: a training plan -- every forward drops.  Each ResBlock's out_layers.0
+                               finalize runs on its own and one cwdm_gn_silu_dropout pass writes the masked,
+                               activated input of out_layers.3 (site = the ResBlock's ordinal in forward order,
+                               seed = cwdm_unet_set_dropout_seed); the backward masks that conv's input gradient
+                               with cwdm_dropout_bwd.  Same parameters and packed layouts as with 0.  Not with
+                               use_freq.  0.0 (and a zeroed struct): off, the plan is unchanged */
 } cwdm_unet_config;
 
 int cwdm_unet_create(const cwdm_unet_config* cfg, cwdm_unet** plan);
+/* The 64-bit seed of a dropout plan's masks: host state of the plan, read whenever a forward or a backward
+ * launches (not captured on the stream).  Set it before a forward and again, to the same value, before that
+ * forward's backward: forwards and backwards of several calls may then interleave. */
+int cwdm_unet_set_dropout_seed(cwdm_unet* plan, uint64_t seed);
 void cwdm_unet_destroy(cwdm_unet* plan);
 int cwdm_unet_num_params(const cwdm_unet* plan);
 int cwdm_unet_param_info(const cwdm_unet* plan, int i, char* name, int name_cap,

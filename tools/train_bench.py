@@ -8,7 +8,7 @@ all-reduce overlapped when WORLD_SIZE > 1), fused AdamW over the flat
 parameters.  Prints one JSON line on rank 0 with steps/s (all ranks), the
 forward/backward conv TFLOP/s and the fraction of the dense bf16 MFMA peak.
 
-usage: python tools/train_bench.py [--grid 128] [--steps 5] [--dtype bf16]
+usage: python tools/train_bench.py [--grid 128] [--steps 5] [--dtype bf16] [--dropout P]
        python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/train_bench.py
 """
 import argparse
@@ -35,13 +35,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--dropout", type=float, default=0.0, help="UNetModel(dropout=P): the ResBlocks' in-kernel "
+                    "Philox dropout (0 = the plan without it)")
     args = ap.parse_args()
     from guided_diffusion import dist_util, script_util, train_util
     os.environ.setdefault("CWDM_LOGDIR", os.path.join(ROOT, "gpurun_out", "train_bench"))
     dist_util.setup_dist()
     rank, world = dist.get_rank(), dist.get_world_size()
     dev = dist_util.dev()
-    margs = script_util.run_sh_model_args(diffusion_steps=1000, sample_schedule="direct")
+    margs = script_util.run_sh_model_args(diffusion_steps=1000, sample_schedule="direct", dropout=args.dropout)
     keys = script_util.model_and_diffusion_defaults().keys()
     model, diffusion = script_util.create_model_and_diffusion(**{k: margs[k] for k in keys},
                                                               compute_dtype=args.dtype)
@@ -78,7 +80,7 @@ def main():
             "metric": "training steps/s (TrainLoop.run_step, i2i cWDM, 128^3 subbands)",
             "value": round(world * args.batch * args.steps / dt, 4), "unit": "volumes/s",
             "n_gpus": world, "steps": args.steps, "ms_per_step": round(per_step * 1e3, 2),
-            "dtype": args.dtype, "grid": g, "batch_per_gpu": args.batch,
+            "dtype": args.dtype, "grid": g, "batch_per_gpu": args.batch, "dropout": args.dropout,
             "conv_tflop_per_step": round((ffl + bfl) / 1e12, 2),
             "conv_tflops_achieved": round((ffl + bfl) / per_step / 1e12, 1),
             "mfma_frac": round((ffl + bfl) / per_step / 1e12 / peak, 4),
