@@ -340,6 +340,9 @@ def _run_conv_case(case, dtype_name, split):
     s = st.sum(1).cpu()
     ref_sum = ref.sum(dim=(2, 3, 4))
     assert torch.allclose(s[..., 0], ref_sum, rtol=1e-3, atol=1e-2 * ref.abs().max().item() * 8)
+    # ... and their squares (the bound of test_gpu_up_phase.py; exact and derived bounds: test_gpu_conv_exact.py)
+    ref_sq = (ref.double() ** 2).sum(dim=(2, 3, 4))
+    assert torch.allclose(s[..., 1].double(), ref_sq, rtol=1e-3, atol=1e-2 * ref.abs().max().item() ** 2 * 8), name
 
 
 V4_CASES = [
@@ -349,6 +352,9 @@ V4_CASES = [
     ("v4_up_res", 1, (8, 4, 64), 32, 0, 128, 1, True, False, 1),
     ("v4_concat_nogn", 1, (4, 12, 32), 16, 32, 128, 0, False, False, 0),
     # K-split work items (fewer tiles than CU slots): partial slices + finish pass
+    # (v4_ksplit_gn_skip, like v4_gn_concat_skip_res above, has a 1x1 skip AND a residual, which the DMA path
+    # refuses: on every path these two run on the brick kernels -- test_gpu_conv_exact.py,
+    # test_skip_plus_residual_shapes_are_brick_cases; its v4 cases use the same shapes without the residual)
     ("v4_ksplit_gn_skip", 1, (8, 4, 32), 96, 32, 128, 0, True, True, 0),
     ("v4_ksplit_up", 2, (8, 8, 32), 64, 0, 64, 1, True, False, 1),
     # W not a multiple of 32: the last x tile is partial (masked stores / statistics)
@@ -368,8 +374,10 @@ V4_CASES = [
 def test_conv3d_dma_kernel_vs_torch(case, dtype_name, path):
     """The DMA-staged wide-grid kernels, forced on small shapes, against
     F.conv3d: path 3 = conv3d_v4.hpp (GroupNorm pre-pass, K split), path 2 =
-    the warp-specialised conv3d_v5.hip for 16-bit shapes it takes (GroupNorm +
-    SiLU in LDS, helper-wave epilogue; fp32 stays on v4)."""
+    the warp-specialised conv3d_v5.hip for 16-bit shapes it takes (helper-wave
+    epilogue; GroupNorm by the same pre-pass at the default CWDM_V5 = 3, in LDS
+    only with CWDM_V5 = 1 / 2; fp32 stays on v4).  A case with a 1x1 skip and a
+    residual runs on the brick kernels whatever the path (see V4_CASES)."""
     from cwdm_hip._lib import lib
     L = lib()
     prev = L.cwdm_conv3d_set_path(path)
