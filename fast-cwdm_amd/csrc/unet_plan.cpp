@@ -2,7 +2,8 @@
 // family (guided_diffusion/unet.py:482-725), owns the parameter
 // naming contract (state_dict keys/shapes), packs weights into the kernel
 // layouts and replays UNetModel.forward (unet.py:754-800) as a fixed list of
-// GroupNorm-finalize and fused conv launches on one stream.
+// GroupNorm-finalize and fused conv launches on one stream (struct Forward, one
+// member per StepKind).
 //
 // build() also records the model as a list of Blocks, each of one BlockKind:
 // the gradient segments of the training backward.  cwdm_unet_backward runs a
@@ -184,8 +185,8 @@ struct cwdm_unet {
   struct Alias { std::string name; int owner, before; };
   std::vector<Alias> aliases;     // WavUNetModel: second state_dict name of a reused parameter; before = the
                                   // parameter index it precedes in state_dict order
-  std::vector<int> trace;         // tensor id per topology block (-1 = final output)
-  std::vector<int> trace_level;
+  struct Trace { int tensor, level; };
+  std::vector<Trace> trace;       // per topology block: its output tensor (-1 = final output) and level
   int input_tensor = -1;          // pseudo tensor for x
   int R = 0;                      // emb projection rows
   std::vector<int> emb_rows_w, emb_rows_b, emb_rows_cb;  // per res block: emb weight/bias param, conv1 bias param
@@ -233,6 +234,7 @@ void build(cwdm_unet* u) {
     return (int)u->tensors.size() - 1;
   };
   u->input_tensor = new_tensor(0, c.in_channels);
+  auto trace = [&](int tensor, int lvl) { u->trace.push_back({tensor, lvl}); };
 
   // WavUNetModel's decoder registers one ResBlock under two prefixes
   // (wunet.py:648-687): while alias_from is set, names under it resolve to the
@@ -265,8 +267,7 @@ void build(cwdm_unet* u) {
     h = cs.out = new_tensor(0, mc);
     u->convs.push_back(cs);
     u->steps.push_back({kConv, (int)u->convs.size() - 1});
-    u->trace.push_back(h);
-    u->trace_level.push_back(0);
+    trace(h, 0);
   }
   std::vector<int> stack{h};
   int level = 0;
@@ -484,14 +485,14 @@ void build(cwdm_unet* u) {
       for (int r = 0; r < c.num_res_blocks; ++r) {
         h = resblock("input_blocks." + std::to_string(idx) + ".0", h, -1, mult * mc, BK::Res);
         ch = mult * mc;
-        u->trace.push_back(h); u->trace_level.push_back(level);
+        trace(h, level);
         ++idx;
       }
       int sk = -1;
       h = resblock("input_blocks." + std::to_string(idx) + ".0", h, -1, ch, BK::WavDown, -1, &sk);
       skips.push_back(sk);
       ++level;
-      u->trace.push_back(h); u->trace_level.push_back(level);
+      trace(h, level);
       // WaveletDownsample (:131-145): conv(cat(8 bands) / 3) + h
       const int cp = u->tensors[pyr].channels;
       HaarStep hp{};
@@ -514,13 +515,13 @@ void build(cwdm_unet* u) {
       pb.c1 = (int)u->convs.size() - 1;
       pb.p_end = (int)u->params.size();
       u->blocks.push_back(pb);
-      u->trace.push_back(h); u->trace_level.push_back(level);
+      trace(h, level);
       idx += 2;
     }
     h = resblock("middle_block.0", h, -1, ch, BK::Res);
-    u->trace.push_back(h); u->trace_level.push_back(level);
+    trace(h, level);
     h = resblock("middle_block.1", h, -1, ch, BK::Res);
-    u->trace.push_back(h); u->trace_level.push_back(level);
+    trace(h, level);
     idx = 0;
     for (int l = nl - 1; l >= 0; --l) {
       const int mult = c.channel_mult[l];
@@ -542,13 +543,13 @@ void build(cwdm_unet* u) {
           h = resblock(p + ".1", h, -1, ch, BK::WavUp, sk);
           --level;
         }
-        u->trace.push_back(h); u->trace_level.push_back(level);
+        trace(h, level);
         ++idx;
       }
     }
     for (int i = 0; i < c.num_res_blocks; ++i) {
       h = resblock("out_res." + std::to_string(i) + ".0", h, -1, ch, BK::Res);
-      u->trace.push_back(h); u->trace_level.push_back(level);
+      trace(h, level);
     }
   }
   for (int l = 0; l < nl && !c.use_freq; ++l) {
@@ -557,7 +558,7 @@ void build(cwdm_unet* u) {
       h = resblock("input_blocks." + std::to_string(idx) + ".0", h, -1, mult * mc, BK::Res);
       ch = mult * mc;
       stack.push_back(h);
-      u->trace.push_back(h); u->trace_level.push_back(level);
+      trace(h, level);
       ++idx;
     }
     if (l != nl - 1) {
@@ -565,13 +566,13 @@ void build(cwdm_unet* u) {
       h = c.resblock_updown ? resblock(p, h, -1, ch, BK::ResDown) : resample_layer(p + ".op", h, 1);
       ++level;
       stack.push_back(h);
-      u->trace.push_back(h); u->trace_level.push_back(level);
+      trace(h, level);
       ++idx;
     }
   }
   if (!c.use_freq) {
     h = resblock("middle_block.0", h, -1, ch, BK::Res);
-    u->trace.push_back(h); u->trace_level.push_back(level);
+    trace(h, level);
     if (c.bottleneck_attention) {
       // AttentionBlock (unet.py:314-360): norm, qkv, proj_out in state_dict order; the ResBlock after it
       // is then middle_block.2
@@ -594,10 +595,10 @@ void build(cwdm_unet* u) {
       blk.attn = (int)u->attns.size() - 1;
       blk.p_end = (int)u->params.size();
       u->blocks.push_back(blk);
-      u->trace.push_back(h); u->trace_level.push_back(level);
+      trace(h, level);
     }
     h = resblock(c.bottleneck_attention ? "middle_block.2" : "middle_block.1", h, -1, ch, BK::Res);
-    u->trace.push_back(h); u->trace_level.push_back(level);
+    trace(h, level);
     idx = 0;
   }
   for (int l = nl - 1; l >= 0 && !c.use_freq; --l) {
@@ -620,12 +621,12 @@ void build(cwdm_unet* u) {
         h = resblock("output_blocks." + std::to_string(idx) + ".0", h, skip, mc * mult, BK::Res);
         ch = mc * mult;
       }
-      u->trace.push_back(h); u->trace_level.push_back(level);
+      trace(h, level);
       if (l && i == c.num_res_blocks) {
         const std::string p = "output_blocks." + std::to_string(idx) + ".1";
         h = c.resblock_updown ? resblock(p, h, -1, ch, BK::ResUp) : resample_layer(p + ".conv", h, 0);
         --level;
-        u->trace.push_back(h); u->trace_level.push_back(level);
+        trace(h, level);
       }
       ++idx;
     }
@@ -643,7 +644,7 @@ void build(cwdm_unet* u) {
   u->convs.push_back(co);
   u->head_c = (int)u->convs.size() - 1;
   u->steps.push_back({kConv, (int)u->convs.size() - 1});
-  u->trace.push_back(-1); u->trace_level.push_back(0);
+  trace(-1, 0);
 
   // packed layout
   int64_t off = 0;
@@ -718,6 +719,44 @@ void build(cwdm_unet* u) {
   u->packed_bwd_bytes = bo;
 }
 
+// shape-only descriptor of one conv step (pointers filled in by Forward::conv_desc)
+cwdm_conv3d_desc conv_shape(const cwdm_unet* u, const ConvStep& cs, int64_t B, int64_t D, int64_t H, int64_t W) {
+  cwdm_conv3d_desc d{};
+  d.dtype = u->cfg.dtype;
+  d.B = B; d.D = D >> cs.level; d.H = H >> cs.level; d.W = W >> cs.level;
+  d.cout = cs.cout;
+  d.a_c0 = u->tensors[cs.a0].channels;
+  d.a_c1 = cs.a1 >= 0 ? u->tensors[cs.a1].channels : 0;
+  d.a_mode = cs.amode;
+  // presence flags only: they select the kernel path and size its workspace
+  // (the DMA-staged kernel needs room for the GroupNorm+SiLU'd input and the skip)
+  d.a_w = reinterpret_cast<const void*>(1);
+  if (cs.gn >= 0) d.a_gn = reinterpret_cast<const float*>(1);
+  if (cs.ws_p >= 0) {
+    d.b_c0 = u->tensors[cs.sb0].channels;
+    d.b_c1 = cs.sb1 >= 0 ? u->tensors[cs.sb1].channels : 0;
+    d.b_w = reinterpret_cast<const void*>(1);  // presence flag only
+  }
+  d.res_mode = cs.rmode;
+  d.out_dtype = cs.out < 0 ? CWDM_F32 : u->cfg.dtype;
+  if (cs.wsplit_off >= 0) d.a_w_split = reinterpret_cast<const void*>(1);   // presence flags only
+  if (cs.wphase_off >= 0) d.a_w_phase = reinterpret_cast<const void*>(1);
+  return d;
+}
+// voxels per batch of such a conv's source grid: half the output's edges under the nearest x2 gather (a_mode 1)
+int64_t src_voxels(const cwdm_conv3d_desc& d) {
+  return d.a_mode == 1 ? (d.D / 2) * (d.H / 2) * (d.W / 2) : d.D * d.H * d.W;
+}
+// the 1x1 skip of conv d alone, as an fp32 product: no 3x3x3 operand, bias, statistics or residual
+// (not cwdm::skip_desc, which keeps the residual and the conv's output dtype)
+cwdm_conv3d_desc skip_only_desc(const cwdm_conv3d_desc& d) {
+  cwdm_conv3d_desc k = d;
+  k.a0 = k.a1 = nullptr; k.a_c0 = k.a_c1 = 0; k.a_gn = nullptr; k.a_w = nullptr; k.a_mode = 0;
+  k.bias = nullptr; k.bias_bstride = 0; k.stats = nullptr; k.res = nullptr; k.res_mode = -1;
+  k.out_dtype = CWDM_F32;
+  return k;
+}
+
 // the accurate fast mode on a small grid: the fp32 conv d (GroupNorm+SiLU'd or plain input, optional 1x1
 // skip) as ONE bf16 small-grid conv over the K-expanded split input [hi | lo | hi] of SiLU(GN(x))
 // (cwdm::split3_prep, chunk-major) against the weights [hi | hi | lo] (cs.xsplit_off): the three
@@ -738,7 +777,6 @@ struct XsgPlan {
 XsgPlan xsg_plan(const ConvStep& cs, const cwdm_conv3d_desc& d) {
   XsgPlan x;
   if (cs.xsplit_off < 0 || d.res_mode > 1 || (d.b_w && d.res_mode >= 0)) return x;
-  const int64_t sv = cs.amode == 1 ? (d.D / 2) * (d.H / 2) * (d.W / 2) : d.D * d.H * d.W;
   const int C = d.a_c0 + d.a_c1;
   cwdm_conv3d_desc e = d;
   e.dtype = CWDM_BF16;
@@ -752,17 +790,14 @@ XsgPlan xsg_plan(const ConvStep& cs, const cwdm_conv3d_desc& d) {
   x.er = cwdm::conv_route_prepared(&e, e.res_mode, cx);
   if (x.er.kernel != cwdm::ConvKernel::SmallGrid) return x;
   x.e = e;
-  x.x3_bytes = align_up(d.B * sv * 3 * C * 2);
+  x.x3_bytes = align_up(d.B * src_voxels(d) * 3 * C * 2);
   x.skip_bytes = d.b_w ? align_up(d.B * d.D * d.H * d.W * d.cout * 4) : 0;
   // a K-split slice holds the grid's whole 256-voxel statistics bricks
   const int64_t slice = d.B * cwdm_conv3d_parts(e.dtype, d.D, d.H, d.W, d.cout) * 256 * d.cout * 4;
   int64_t part = x.er.ksplit > 1 ? x.er.ksplit * slice : 0;
   if (d.b_w) {
     // the skip alone: K-expanded on the small-grid kernel's 1x1 form where its weights were packed, else as fp32
-    cwdm_conv3d_desc k = d;
-    k.a0 = k.a1 = nullptr; k.a_c0 = k.a_c1 = 0; k.a_gn = nullptr; k.a_w = nullptr; k.a_mode = 0;
-    k.bias = nullptr; k.bias_bstride = 0; k.stats = nullptr; k.res = nullptr; k.res_mode = -1;
-    k.out_dtype = CWDM_F32;
+    cwdm_conv3d_desc k = skip_only_desc(d);
     x.sk_pw_split = cwdm::conv_route_skip(&k, cx).skip == cwdm::SkipKernel::PwSplit;
     k.dtype = CWDM_BF16;
     k.a_w_split = nullptr;
@@ -781,13 +816,14 @@ XsgPlan xsg_plan(const ConvStep& cs, const cwdm_conv3d_desc& d) {
   return x;
 }
 
-// how the forward runs one conv step, decided in layout()
+// how the forward runs one conv step, decided in layout(); Forward::conv dispatches to the member named here
 enum class ConvKind {
-  Plain,       // cwdm::conv3d_forward with the plan's context
-  SkipPass,    // conv1 of a skip block behind the fused GroupNorm + 1x1-skip pass (cwdm::gn_apply_skip)
-  SkipTaken,   // conv2 of that block: its skip product came from conv1's pass, a plain residual here
-  HeadSplit,   // the accurate fast mode's head over the K-expanded split input
-  Xsg          // the accurate fast mode on a small grid (XsgPlan)
+  Plain,       // conv_plain: cwdm::conv3d_forward with the plan's context
+  SkipPass,    // conv_skip_pass: conv1 of a skip block behind the fused GroupNorm + 1x1-skip pass (cwdm::gn_apply_skip)
+  SkipTaken,   // conv2 of that block: its skip product came from conv1's pass, so conv() rewrites the desc to a
+               // plain residual and runs conv_plain
+  HeadSplit,   // conv_head_split: the accurate fast mode's head over the K-expanded split input
+  Xsg          // conv_xsg: the accurate fast mode on a small grid (XsgPlan)
 };
 struct ConvPlan {
   cwdm::ConvRoute route;   // of the conv's shape in the plan's context, nothing offered
@@ -815,30 +851,27 @@ struct Layout {
   int64_t train_total;
 };
 
-// shape-only descriptor of one conv step (pointers filled in by the forward)
-cwdm_conv3d_desc conv_shape(const cwdm_unet* u, const ConvStep& cs, int64_t B, int64_t D, int64_t H, int64_t W) {
-  cwdm_conv3d_desc d{};
-  d.dtype = u->cfg.dtype;
-  d.B = B; d.D = D >> cs.level; d.H = H >> cs.level; d.W = W >> cs.level;
-  d.cout = cs.cout;
-  d.a_c0 = u->tensors[cs.a0].channels;
-  d.a_c1 = cs.a1 >= 0 ? u->tensors[cs.a1].channels : 0;
-  d.a_mode = cs.amode;
-  // presence flags only: they select the kernel path and size its workspace
-  // (the DMA-staged kernel needs room for the GroupNorm+SiLU'd input and the skip)
-  d.a_w = reinterpret_cast<const void*>(1);
-  if (cs.gn >= 0) d.a_gn = reinterpret_cast<const float*>(1);
-  if (cs.ws_p >= 0) {
-    d.b_c0 = u->tensors[cs.sb0].channels;
-    d.b_c1 = cs.sb1 >= 0 ? u->tensors[cs.sb1].channels : 0;
-    d.b_w = reinterpret_cast<const void*>(1);  // presence flag only
-  }
-  d.res_mode = cs.rmode;
-  d.out_dtype = cs.out < 0 ? CWDM_F32 : u->cfg.dtype;
-  if (cs.wsplit_off >= 0) d.a_w_split = reinterpret_cast<const void*>(1);   // presence flags only
-  if (cs.wphase_off >= 0) d.a_w_phase = reinterpret_cast<const void*>(1);
-  return d;
-}
+// what both passes read of one call (the base of struct Forward and struct Backward): the plan, the layout
+// of the forward's workspace for the call's grid, the base pointers, and the lookups over them
+struct PlanView {
+  cwdm_unet* u;
+  const Layout& L;
+  const unsigned char* pk;   // packed parameters (forward form)
+  unsigned char* wb;         // the forward's workspace (the backward only reads it)
+  const void* x;             // the model input
+  int64_t B, D, H, W;
+  cwdm_stream_t stream;
+  // derived from the above
+  hipStream_t s = (hipStream_t)stream;
+  int dt = u->cfg.dtype;
+
+  const float* P(int64_t off) const { return reinterpret_cast<const float*>(pk + off); }
+  const void* act(int id) const { return id < 0 ? nullptr : (id == u->input_tensor ? x : wb + L.t_off[id]); }
+  int nch(int id) const { return id < 0 ? 0 : u->tensors[id].channels; }
+  int64_t vox(int lv) const { return (D >> lv) * (H >> lv) * (W >> lv); }
+  const float* ss_of(int g) const { return reinterpret_cast<const float*>(wb + L.ss_off[g]); }
+  const float* mr_of(int g) const { return reinterpret_cast<const float*>(wb + L.mr_off[g]); }
+};
 
 // statistics partial rows per tensor: the per-tile layout, or the rows of a warp-specialised conv
 // that summed them per workgroup (ConvCall::stats_rows; env CWDM_STATS_WG=0: per tile everywhere)
@@ -941,8 +974,7 @@ Layout layout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) {
     const auto& cs = u->convs[i];
     if (!dtype_half(u->cfg.dtype) || cs.gn < 0 || cs.amode > 1 || cs.s2 || !L.conv[i].route.v4_ok) continue;
     const cwdm_conv3d_desc d = conv_shape(u, cs, B, D, H, W);
-    const int64_t sv = cs.amode == 1 ? (d.D / 2) * (d.H / 2) * (d.W / 2) : d.D * d.H * d.W;
-    const int64_t cin = d.a_c0 + d.a_c1;
+    const int64_t sv = src_voxels(d), cin = d.a_c0 + d.a_c1;
     if (sv * cin * 2 >= (1LL << 31)) continue;  // the DMA wgrad's per-batch buffer range
     L.keep_off[i] = take(B * sv * cin * es);
   }
@@ -1246,8 +1278,310 @@ static cwdm_attention_desc attn_desc(const AttnStep& at, int dt, int64_t B, int6
   return ad;
 }
 
-// samp: run the sampling step on the output (cwdm_unet_forward_step); fused
-// into the output head when it qualifies (*fused = 1), else after the forward.
+namespace {
+
+// One forward call: UNetModel.forward as the plan's step list on one stream.  run() dispatches each step to
+// the member of its StepKind (pool, s2d, haar, dropout, avg, attention, gn, conv); conv() fills the step's
+// desc (conv_desc) and dispatches to the member of its ConvKind (conv_plain, conv_skip_pass, conv_head_split,
+// conv_xsg), or to conv_head_sampler where the output head can fuse the sampling step.
+// The pending GroupNorm finalize: gn() only notes its norm in fin_pend (cwdm::GnFinFuse: at the small grids
+// the consumer conv's pre-pass computes it), flush_fin() runs it as its own launch, offer_fin() hands it to a
+// conv that reads that norm and must then take it.  The rule, in run(): a pending finalize whose consumer is
+// not the next step runs before that step.  Env CWDM_GNFIN=0: every finalize as its own launch (A/B switch).
+struct Forward : PlanView {
+  float* out; const float* t;
+  bool keep;                       // a training-sized workspace: keep the convs' activated inputs for the backward
+  const cwdm_sampler_args* samp;   // cwdm_unet_forward_step: run the sampling step on the output, fused into the
+  int* fused;                      // output head where it qualifies (*fused = 1), else by the caller afterwards
+  // derived from the above
+  float* temb = reinterpret_cast<float*>(wb + L.temb);
+  float* ebias = reinterpret_cast<float*>(wb + L.ebias);
+  unsigned* sync = reinterpret_cast<unsigned*>(wb + L.sync);   // the zeroed sync block (ConvCall::sync)
+  // statistics partial rows per tensor: the per-tile layout, or a conv's per-workgroup rows (plan_stats_wg)
+  std::vector<int64_t> srows = L.s_parts;
+  int fin_pend = -1;   // the norm whose finalize is pending, -1 none
+  int conv_i = 0;      // the profiling cursor: conv steps run so far (u->hooks, u->ev_used)
+
+  void* dst(int id) const { return wb + L.t_off[id]; }
+  float* stats(int id) const { return reinterpret_cast<float*>(wb + L.s_off[id]); }
+  void* kept(int ci) const { return keep && L.keep_off[ci] >= 0 ? wb + L.keep_off[ci] : nullptr; }
+
+  int begin() {
+    CWDM_HIP(hipMemsetAsync(sync, 0, cwdm::plan_sync_bytes(), s));
+    if (int rc = launch_time_embed(t, (int)B, u->cfg.model_channels, P(u->off_te_w1), P(u->off_te_b1), P(u->off_te_w2),
+                                   P(u->off_te_b2), temb, s))
+      return rc;
+    if (int rc = launch_emb_proj(temb, (int)B, u->E, P(u->off_emb_w), P(u->off_emb_b), u->R, ebias, s)) return rc;
+    return u->profiling ? prof_begin() : CWDM_OK;
+  }
+  // four events per conv: the MFMA kernel launches inside it (cwdm::ProfHook)
+  int prof_begin() {
+    const size_t need = u->convs.size() * 4;
+    while (u->ev.size() < need) {
+      hipEvent_t e;
+      CWDM_HIP(hipEventCreate(&e));
+      u->ev.push_back(e);
+    }
+    u->ev_flops.assign(u->convs.size(), 0.0);
+    u->hooks.assign(u->convs.size(), cwdm::ProfHook{});
+    for (size_t i = 0; i < u->convs.size(); ++i)
+      for (int k = 0; k < 4; ++k) u->hooks[i].ev[k >> 1][k & 1] = u->ev[4 * i + k];
+    u->ev_used = 0;
+    return CWDM_OK;
+  }
+
+  int run() {
+    int rc = CWDM_OK;
+    for (const auto& st : u->steps) {
+      if (fin_pend >= 0 && !(st.kind == kConv && u->convs[st.idx].gn == u->gns[fin_pend].ss_id) && (rc = flush_fin()))
+        return rc;
+      switch (st.kind) {
+        case kGn: rc = gn(st.idx); break;
+        case kConv: rc = conv(st.idx); break;
+        case kPool: rc = pool(u->pools[st.idx]); break;
+        case kS2d: rc = s2d(u->s2ds[st.idx]); break;
+        case kHaar: rc = haar(u->haars[st.idx]); break;
+        case kAvg: rc = avg(u->avgs[st.idx]); break;
+        case kAttn: rc = attention(u->attns[st.idx]); break;
+        case kDrop: rc = dropout(u->drops[st.idx]); break;
+      }
+      if (rc) return rc;
+    }
+    return flush_fin();
+  }
+
+  // ---- the pending GroupNorm finalize
+  int gn(int gi) {
+    static const bool fin_on = env_not0("CWDM_GNFIN");
+    fin_pend = gi;
+    return fin_on ? CWDM_OK : flush_fin();
+  }
+  // the pending finalize's arguments (not yet used); it is pending no longer
+  cwdm::GnFinFuse take_fin() {
+    const auto& g = u->gns[std::exchange(fin_pend, -1)];
+    cwdm::GnFinFuse f{};
+    f.s0 = stats(g.src0); f.p0 = srows[g.src0]; f.c0 = nch(g.src0);
+    f.s1 = g.src1 >= 0 ? stats(g.src1) : nullptr;
+    f.p1 = g.src1 >= 0 ? srows[g.src1] : 0; f.c1 = nch(g.src1);
+    f.gamma = P(g.gamma_off); f.beta = P(g.beta_off); f.groups = u->cfg.num_groups;
+    f.voxels = vox(g.level); f.eps = 1e-5f; f.B = B;
+    f.ss = reinterpret_cast<float*>(wb + L.ss_off[g.ss_id]); f.mr = reinterpret_cast<float*>(wb + L.mr_off[g.ss_id]);
+    f.film = g.film_row >= 0 ? ebias + g.film_row : nullptr;
+    f.film_bs = u->R;
+    return f;
+  }
+  int flush_fin() {
+    if (fin_pend < 0) return CWDM_OK;
+    const cwdm::GnFinFuse f = take_fin();
+    if (f.film)
+      return cwdm_gn_finalize_film(f.s0, f.p0, f.c0, f.s1, f.p1, f.c1, f.gamma, f.beta, f.groups, B, f.voxels, f.eps,
+                                   f.ss, f.mr, f.film, f.film_bs, stream);
+    return cwdm_gn_finalize(f.s0, f.p0, f.c0, f.s1, f.p1, f.c1, f.gamma, f.beta, f.groups, B, f.voxels, f.eps, f.ss,
+                            f.mr, stream);
+  }
+  // conv ci = d through cwdm::conv3d_forward, offered the pending finalize (in ff) if it is of the norm d reads:
+  // the conv must then take it; any other pending finalize runs first
+  int offer_fin(int ci, const cwdm_conv3d_desc& d, cwdm::ConvCall& cc, cwdm::GnFinFuse& ff) {
+    const bool offer = fin_pend >= 0 && d.a_gn == ss_of(u->gns[fin_pend].ss_id);
+    if (offer) {
+      ff = take_fin();
+      cc.gnfin = &ff;
+    } else if (int rc = flush_fin()) {
+      return rc;
+    }
+    if (int rc = cwdm::conv3d_forward(&d, cc, s)) return rc;
+    CWDM_REQUIRE(!offer || ff.used, CWDM_E_INVALID,
+                 "cwdm_unet_forward: conv " + std::to_string(ci) + " did not take its GroupNorm finalize");
+    return CWDM_OK;
+  }
+
+  // ---- the steps that are one launch (dropout and attention read a norm no conv takes: run() flushed it)
+  int pool(const PoolStep& ps) {
+    const int lv = ps.level_out;
+    return cwdm_gn_silu_pool(act(ps.src), ps.channels, ss_of(ps.ss_id), B, D >> lv, H >> lv, W >> lv, dt,
+                             dst(ps.out_h), dst(ps.out_x), stream);
+  }
+  int s2d(const S2dStep& sd) {
+    const int lv = sd.level_out;
+    return cwdm_space_to_depth(act(sd.src), sd.channels, B, D >> lv, H >> lv, W >> lv, dt, dst(sd.out), 1, 0, stream);
+  }
+  int haar(const HaarStep& hs) {
+    const int lv = hs.level;
+    cwdm_haar_nd_desc a{};
+    a.dtype = dt; a.B = B; a.d = D >> lv; a.h = H >> lv; a.w = W >> lv; a.C = nch(hs.src);
+    a.inverse = hs.inverse; a.all8 = hs.all8;
+    a.src = act(hs.src); a.high_in = act(hs.high_in);
+    a.lll_scale = hs.lll_scale; a.high_scale = hs.high_scale;
+    a.out = dst(hs.out); a.high_out = hs.high_out >= 0 ? dst(hs.high_out) : nullptr;
+    a.bias = hs.emb_row >= 0 ? ebias + hs.emb_row : nullptr; a.bias_bstride = u->R;
+    a.stats = hs.stats ? stats(hs.out) : nullptr;
+    return cwdm_haar_nd(&a, stream);
+  }
+  int dropout(const DropStep& ds) {
+    return cwdm_gn_silu_dropout(act(ds.src), ss_of(ds.ss_id), dst(ds.out), dt, B, vox(ds.level), ds.channels,
+                                u->cfg.dropout, u->dropout_seed, ds.site, stream);
+  }
+  int avg(const AvgStep& as) {
+    return cwdm_skip_avg(act(as.a), act(as.b), dst(as.out), stats(as.out), dt, B, vox(as.level), as.channels, stream);
+  }
+  // qkv(GroupNorm(src)), attention, src + proj_out; a training-sized workspace keeps the normalised input and
+  // the rows' log-sum-exp
+  int attention(const AttnStep& at) {
+    const int64_t T = vox(at.level);
+    const int C = at.C;
+    unsigned char* qkv = wb + L.attn_qkv;
+    void* a = wb + L.attn_a;
+    int rc;
+    if ((rc = cwdm::attn_linear(dt, B, T, C, 3 * C, act(at.src), ss_of(at.gn), pk + at.qkv_w_off, P(at.qkv_b_off),
+                                nullptr, qkv, keep ? wb + L.attn_n : nullptr, nullptr, s)))
+      return rc;
+    const cwdm_attention_desc ad =
+        attn_desc(at, dt, B, T, qkv, a, keep ? reinterpret_cast<float*>(wb + L.attn_L) : nullptr);
+    if ((rc = cwdm_attention_forward(&ad, stream))) return rc;
+    return cwdm::attn_linear(dt, B, T, C, C, a, nullptr, pk + at.proj_w_off, P(at.proj_b_off), act(at.src),
+                             dst(at.out), nullptr, stats(at.out), s);
+  }
+
+  // ---- a conv step
+  cwdm_conv3d_desc conv_desc(int ci) const {
+    const auto& cs = u->convs[ci];
+    // (conv_shape set the channel counts, a_mode, res_mode and out_dtype; its presence flags become pointers)
+    cwdm_conv3d_desc d = conv_shape(u, cs, B, D, H, W);
+    d.a0 = act(cs.a0); d.a1 = act(cs.a1);
+    d.workspace = wb + L.split; d.ws_bytes = L.split_bytes;
+    d.a_gn = cs.gn >= 0 ? ss_of(cs.gn) : nullptr;
+    d.a_w = pk + cs.w_off;
+    d.a_w_split = cs.wsplit_off >= 0 ? pk + cs.wsplit_off : nullptr;
+    d.a_w_phase = cs.wphase_off >= 0 ? pk + cs.wphase_off : nullptr;
+    if (cs.ws_p >= 0) { d.b0 = act(cs.sb0); d.b1 = act(cs.sb1); d.b_w = pk + cs.wsk_off; }
+    if (cs.bias_kind == 0) { d.bias = P(cs.bias_off); d.bias_bstride = 0; }
+    else { d.bias = ebias + cs.bias_off; d.bias_bstride = u->R; }
+    d.res = act(cs.res);
+    d.out = cs.out < 0 ? out : dst(cs.out);
+    d.stats = (cs.stats && cs.out >= 0) ? stats(cs.out) : nullptr;
+    return d;
+  }
+  int conv(int ci) {
+    const auto& cs = u->convs[ci];
+    cwdm_conv3d_desc d = conv_desc(ci);
+    // this conv's context: the plan's zeroed sync block, per-workgroup statistics, the profiling hook
+    cwdm::ConvCall cc;
+    cc.sync = sync; cc.stats_wg = plan_stats_wg();
+    if (u->profiling) cc.prof = &u->hooks[conv_i];
+    ConvKind kind = keep ? L.conv[ci].kind_keep : L.conv[ci].kind;
+    if (kind == ConvKind::SkipTaken) {
+      // the skip was computed in conv1's GroupNorm pass: a plain residual here
+      d.b0 = d.b1 = nullptr; d.b_c0 = d.b_c1 = 0; d.b_w = nullptr;
+      d.res = wb + L.skipbuf; d.res_mode = 0;
+      kind = ConvKind::Plain;
+    }
+    int rc = CWDM_OK;
+    // (the output head fuses the sampling step where the step's arguments allow: a run-time question)
+    if (kind != ConvKind::SkipPass && samp && cs.out < 0 && cwdm::head_sampler_eligible(&d, samp))
+      rc = conv_head_sampler(d, cc);
+    else switch (kind) {
+      case ConvKind::Plain:
+      case ConvKind::SkipTaken: rc = conv_plain(ci, d, cc); break;   // (SkipTaken: rewritten above)
+      case ConvKind::SkipPass: rc = conv_skip_pass(ci, d, cc); break;
+      case ConvKind::HeadSplit: rc = conv_head_split(ci, d, cc); break;
+      case ConvKind::Xsg: rc = conv_xsg(ci, d, cc); break;
+    }
+    if (rc) return rc;
+    if (cc.stats_rows > 0 && cs.out >= 0) srows[cs.out] = cc.stats_rows;
+    if (u->profiling) u->ev_used = conv_i + 1;
+    ++conv_i;
+    return CWDM_OK;
+  }
+  int conv_plain(int ci, const cwdm_conv3d_desc& d, cwdm::ConvCall& cc) {
+    cc.act_keep = kept(ci);
+    cwdm::GnFinFuse ff{};
+    if (int rc = offer_fin(ci, d, cc, ff)) return rc;
+    CWDM_REQUIRE(!cc.act_keep || cc.act_kept, CWDM_E_INVALID,
+                 "cwdm_unet_forward: conv " + std::to_string(ci) + " did not keep its activated input");
+    return CWDM_OK;
+  }
+  int conv_head_sampler(const cwdm_conv3d_desc& d, cwdm::ConvCall& cc) {
+    if (int rc = flush_fin()) return rc;
+    if (int rc = cwdm::head_sampler_forward(&d, samp, cc.prof, s)) return rc;
+    if (fused) *fused = 1;
+    return CWDM_OK;
+  }
+  // conv1 of a skip block: SiLU(GN1(x)) for this conv and W_skip . x for conv2 in one pass
+  int conv_skip_pass(int ci, const cwdm_conv3d_desc& d, cwdm::ConvCall& cc) {
+    const auto& c2 = u->convs[u->convs[ci].skip_conv];
+    const ConvPlan& cp = L.conv[ci];
+    void* ain = kept(ci) ? kept(ci) : wb + L.split;
+    int rc;
+    if ((rc = flush_fin())) return rc;
+    if ((rc = cwdm::gn_apply_skip(d.a0, d.a_c0, d.a1, d.a_c1, d.a_gn, B, d.D * d.H * d.W, dt, pk + c2.wsk_off, c2.cout,
+                                  ain, wb + L.skipbuf, s)))
+      return rc;
+    void* part = wb + L.split + cp.route.ws_act;   // (the K-split slices follow the activated input)
+    return cwdm::v4_launch(&d, ain, d.a_c0 + d.a_c1, nullptr, 0, 1, d.res, d.res_mode, part, cp.pass, cc, s);
+  }
+  // the accurate fast mode's head: a bf16 head over the K-expanded split input (head_split3_prep)
+  int conv_head_split(int ci, const cwdm_conv3d_desc& d, cwdm::ConvCall& cc) {
+    if (int rc = flush_fin()) return rc;
+    void* x3 = wb + L.split;
+    if (int rc = cwdm::head_split3_prep(reinterpret_cast<const float*>(d.a0), d.a_gn, B, d.D * d.H * d.W, d.a_c0, x3, s))
+      return rc;
+    cwdm_conv3d_desc e = d;
+    e.dtype = CWDM_BF16;
+    e.a0 = x3; e.a_c0 = 3 * d.a_c0; e.a1 = nullptr; e.a_c1 = 0;
+    e.a_gn = nullptr; e.a_w = pk + u->convs[ci].hsplit_off; e.a_w_split = nullptr;
+    e.workspace = nullptr; e.ws_bytes = 0;
+    return cwdm::conv3d_forward(&e, cc, s);
+  }
+  // the accurate fast mode on a small grid: one bf16 small-grid conv over the K-expanded split input, its
+  // 1x1 skip first (XsgPlan; workspace x3 | skip | K-split slices)
+  int conv_xsg(int ci, const cwdm_conv3d_desc& d, cwdm::ConvCall& cc) {
+    const auto& cs = u->convs[ci];
+    const XsgPlan& xp = L.xsg[L.conv[ci].xsg];
+    int rc;
+    if ((rc = flush_fin())) return rc;
+    unsigned char* x3 = wb + L.split;
+    const void* res = d.res;   // (the skip's product instead, where there is one)
+    int rmode = d.res_mode;
+    cc.fp32x = true;
+    void* part = x3 + xp.x3_bytes + xp.skip_bytes;
+    if (d.b_w) {
+      if ((rc = xsg_skip(cs, d, xp, part, cc))) return rc;
+      res = x3 + xp.x3_bytes; rmode = 0;
+    }
+    if ((rc = cwdm::split3_prep(reinterpret_cast<const float*>(d.a0), d.a_c0, reinterpret_cast<const float*>(d.a1),
+                                d.a_c1, d.a_gn, B, src_voxels(d), 1, x3, s)))
+      return rc;
+    cwdm_conv3d_desc e = xp.e;
+    e.a0 = x3; e.a1 = nullptr; e.a_w = pk + cs.xsplit_off;
+    e.bias = d.bias; e.bias_bstride = d.bias_bstride;
+    e.res = res; e.res_mode = rmode;
+    e.out = d.out; e.stats = d.stats;
+    e.workspace = nullptr; e.ws_bytes = 0;
+    if (xp.er.ksplit <= 1) part = nullptr;
+    return cwdm::v4_launch(&e, x3, e.a_c0, nullptr, 0, 1, res, rmode, part, xp.er, cc, s);
+  }
+  // its 1x1 skip into the fp32 residual behind x3
+  int xsg_skip(const ConvStep& cs, const cwdm_conv3d_desc& d, const XsgPlan& xp, void* part, cwdm::ConvCall& cc) {
+    unsigned char* x3 = wb + L.split;
+    if (xp.sk_sg) {
+      // the K-expanded split of the raw input on the small-grid kernel
+      if (int rc = cwdm::split3_prep(reinterpret_cast<const float*>(d.b0), d.b_c0, reinterpret_cast<const float*>(d.b1),
+                                     d.b_c1, nullptr, B, d.D * d.H * d.W, 0, x3, s))
+        return rc;
+      cwdm_conv3d_desc k = xp.ek;
+      k.b0 = x3; k.b_w = pk + cs.xsplit_sk_off;
+      return cwdm::sg_skip_launch(&k, x3 + xp.x3_bytes, xp.sk_ksplit > 1 ? part : nullptr, xp.sk_ksplit, cc, s);
+    }
+    // pw_split: the split products of the 1x1 weights
+    cwdm_conv3d_desc k = skip_only_desc(d);
+    k.out = x3 + xp.x3_bytes;
+    k.workspace = nullptr; k.ws_bytes = 0;
+    return xp.sk_pw_split ? cwdm::pw_split_forward(&k, cc.prof, s) : cwdm::conv3d_forward(&k, cc, s);
+  }
+};
+
+}  // namespace
+
 static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, const float* t, float* out,
                              int64_t B, int64_t D, int64_t H, int64_t W, void* ws, int64_t ws_bytes,
                              cwdm_stream_t stream, const cwdm_sampler_args* samp, int* fused) {
@@ -1261,288 +1595,10 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
                "cwdm_unet_forward: workspace too small (need " + std::to_string(L.total) + " bytes)");
   // a training-sized workspace keeps the convs' activated inputs for the backward
   const bool keep = L.train_total > L.total && ws_bytes >= L.train_total;
-  hipStream_t s = (hipStream_t)stream;
-  auto* pk = reinterpret_cast<const unsigned char*>(packed);
-  auto* wb = reinterpret_cast<unsigned char*>(ws);
-  CWDM_HIP(hipMemsetAsync(wb + L.sync, 0, cwdm::plan_sync_bytes(), s));
-  float* temb = reinterpret_cast<float*>(wb + L.temb);
-  float* ebias = reinterpret_cast<float*>(wb + L.ebias);
-  int rc;
-  auto P = [&](int64_t off) { return reinterpret_cast<const float*>(pk + off); };
-  if ((rc = launch_time_embed(t, (int)B, u->cfg.model_channels, P(u->off_te_w1), P(u->off_te_b1), P(u->off_te_w2),
-                              P(u->off_te_b2), temb, s)))
-    return rc;
-  if ((rc = launch_emb_proj(temb, (int)B, u->E, P(u->off_emb_w), P(u->off_emb_b), u->R, ebias, s))) return rc;
-  auto tptr = [&](int id) -> const void* {
-    if (id < 0) return nullptr;
-    if (id == u->input_tensor) return x;
-    return wb + L.t_off[id];
-  };
-  int conv_i = 0;
-  if (u->profiling) {
-    const size_t need = u->convs.size() * 4;
-    while (u->ev.size() < need) {
-      hipEvent_t e;
-      CWDM_HIP(hipEventCreate(&e));
-      u->ev.push_back(e);
-    }
-    u->ev_flops.assign(u->convs.size(), 0.0);
-    u->hooks.assign(u->convs.size(), cwdm::ProfHook{});
-    for (size_t i = 0; i < u->convs.size(); ++i)
-      for (int k = 0; k < 4; ++k) u->hooks[i].ev[k >> 1][k & 1] = u->ev[4 * i + k];
-    u->ev_used = 0;
-  }
-  // GroupNorm finalize offered to its consumer conv (cwdm::GnFinFuse: at the
-  // small grids the conv's pre-pass computes it; any other route runs it
-  // first).  A pending one whose consumer is not the next step runs on its own.
-  // Env CWDM_GNFIN=0: every finalize as its own launch (A/B switch).
-  static const bool fin_on = env_not0("CWDM_GNFIN");
-  // statistics partial rows per tensor: the per-tile layout, or a conv's per-workgroup rows (plan_stats_wg)
-  std::vector<int64_t> srows(L.s_parts);
-  int fin_pend = -1;
-  auto fin_args = [&](int gi, cwdm::GnFinFuse& f) {
-    const auto& g = u->gns[gi];
-    f.s0 = reinterpret_cast<const float*>(wb + L.s_off[g.src0]); f.p0 = srows[g.src0];
-    f.c0 = u->tensors[g.src0].channels;
-    f.s1 = g.src1 >= 0 ? reinterpret_cast<const float*>(wb + L.s_off[g.src1]) : nullptr;
-    f.p1 = g.src1 >= 0 ? srows[g.src1] : 0; f.c1 = g.src1 >= 0 ? u->tensors[g.src1].channels : 0;
-    f.gamma = P(g.gamma_off); f.beta = P(g.beta_off); f.groups = u->cfg.num_groups;
-    f.voxels = (D >> g.level) * (H >> g.level) * (W >> g.level); f.eps = 1e-5f;
-    f.ss = reinterpret_cast<float*>(wb + L.ss_off[g.ss_id]); f.mr = reinterpret_cast<float*>(wb + L.mr_off[g.ss_id]);
-    f.B = B;
-    f.used = false;
-    f.film = g.film_row >= 0 ? ebias + g.film_row : nullptr;
-    f.film_bs = u->R;
-  };
-  auto flush_fin = [&]() -> int {
-    if (fin_pend < 0) return CWDM_OK;
-    cwdm::GnFinFuse f{};
-    fin_args(fin_pend, f);
-    fin_pend = -1;
-    if (f.film)
-      return cwdm_gn_finalize_film(f.s0, f.p0, f.c0, f.s1, f.p1, f.c1, f.gamma, f.beta, f.groups, B, f.voxels, f.eps,
-                                   f.ss, f.mr, f.film, f.film_bs, stream);
-    return cwdm_gn_finalize(f.s0, f.p0, f.c0, f.s1, f.p1, f.c1, f.gamma, f.beta, f.groups, B, f.voxels, f.eps, f.ss,
-                            f.mr, stream);
-  };
-  for (const auto& st : u->steps) {
-    if (fin_pend >= 0 && !(st.kind == kConv && u->convs[st.idx].gn == u->gns[fin_pend].ss_id) && (rc = flush_fin()))
-      return rc;
-    if (st.kind == kPool) {
-      const auto& ps = u->pools[st.idx];
-      const int lv = ps.level_out;
-      if ((rc = cwdm_gn_silu_pool(tptr(ps.src), ps.channels, reinterpret_cast<const float*>(wb + L.ss_off[ps.ss_id]),
-                                  B, D >> lv, H >> lv, W >> lv, u->cfg.dtype, wb + L.t_off[ps.out_h],
-                                  wb + L.t_off[ps.out_x], stream)))
-        return rc;
-      continue;
-    }
-    if (st.kind == kS2d) {
-      const auto& sd = u->s2ds[st.idx];
-      const int lv = sd.level_out;
-      if ((rc = cwdm_space_to_depth(tptr(sd.src), sd.channels, B, D >> lv, H >> lv, W >> lv, u->cfg.dtype,
-                                    wb + L.t_off[sd.out], 1, 0, stream)))
-        return rc;
-      continue;
-    }
-    if (st.kind == kHaar) {
-      const auto& hs = u->haars[st.idx];
-      const int lv = hs.level;
-      cwdm_haar_nd_desc a{};
-      a.dtype = u->cfg.dtype;
-      a.B = B; a.d = D >> lv; a.h = H >> lv; a.w = W >> lv;
-      a.C = u->tensors[hs.src].channels;
-      a.inverse = hs.inverse; a.all8 = hs.all8;
-      a.src = tptr(hs.src); a.high_in = tptr(hs.high_in);
-      a.lll_scale = hs.lll_scale; a.high_scale = hs.high_scale;
-      a.out = wb + L.t_off[hs.out];
-      a.high_out = hs.high_out >= 0 ? wb + L.t_off[hs.high_out] : nullptr;
-      a.bias = hs.emb_row >= 0 ? ebias + hs.emb_row : nullptr;
-      a.bias_bstride = u->R;
-      a.stats = hs.stats ? reinterpret_cast<float*>(wb + L.s_off[hs.out]) : nullptr;
-      if ((rc = cwdm_haar_nd(&a, stream))) return rc;
-      continue;
-    }
-    if (st.kind == kDrop) {
-      // (the norm's finalize ran just above: no conv takes it)
-      const auto& ds = u->drops[st.idx];
-      const int lv = ds.level;
-      if ((rc = cwdm_gn_silu_dropout(tptr(ds.src), reinterpret_cast<const float*>(wb + L.ss_off[ds.ss_id]),
-                                     wb + L.t_off[ds.out], u->cfg.dtype, B, (D >> lv) * (H >> lv) * (W >> lv),
-                                     ds.channels, u->cfg.dropout, u->dropout_seed, ds.site, stream)))
-        return rc;
-      continue;
-    }
-    if (st.kind == kAvg) {
-      const auto& as = u->avgs[st.idx];
-      const int lv = as.level;
-      if ((rc = cwdm_skip_avg(tptr(as.a), tptr(as.b), wb + L.t_off[as.out],
-                              reinterpret_cast<float*>(wb + L.s_off[as.out]), u->cfg.dtype, B,
-                              (D >> lv) * (H >> lv) * (W >> lv), as.channels, stream)))
-        return rc;
-      continue;
-    }
-    if (st.kind == kAttn) {
-      // (the norm's finalize ran just above: no conv takes it)
-      const auto& at = u->attns[st.idx];
-      const int64_t T = (D >> at.level) * (H >> at.level) * (W >> at.level);
-      const int dt = u->cfg.dtype, C = at.C;
-      unsigned char* qkv = wb + L.attn_qkv;
-      void* a = wb + L.attn_a;
-      if ((rc = cwdm::attn_linear(dt, B, T, C, 3 * C, tptr(at.src), reinterpret_cast<const float*>(wb + L.ss_off[at.gn]),
-                                  pk + at.qkv_w_off, P(at.qkv_b_off), nullptr, qkv, keep ? wb + L.attn_n : nullptr,
-                                  nullptr, s)))
-        return rc;
-      const cwdm_attention_desc ad =
-          attn_desc(at, dt, B, T, qkv, a, keep ? reinterpret_cast<float*>(wb + L.attn_L) : nullptr);
-      if ((rc = cwdm_attention_forward(&ad, stream))) return rc;
-      if ((rc = cwdm::attn_linear(dt, B, T, C, C, a, nullptr, pk + at.proj_w_off, P(at.proj_b_off), tptr(at.src),
-                                  wb + L.t_off[at.out], nullptr, reinterpret_cast<float*>(wb + L.s_off[at.out]), s)))
-        return rc;
-      continue;
-    }
-    if (st.kind == kGn) {
-      fin_pend = st.idx;
-      if (!fin_on && (rc = flush_fin())) return rc;
-      continue;
-    }
-    const auto& cs = u->convs[st.idx];
-    cwdm_conv3d_desc d = conv_shape(u, cs, B, D, H, W);
-    d.a0 = tptr(cs.a0);
-    d.a1 = tptr(cs.a1);
-    d.workspace = wb + L.split;
-    d.ws_bytes = L.split_bytes;
-    d.a_gn = cs.gn >= 0 ? reinterpret_cast<const float*>(wb + L.ss_off[cs.gn]) : nullptr;
-    d.a_w = pk + cs.w_off;
-    d.a_w_split = cs.wsplit_off >= 0 ? pk + cs.wsplit_off : nullptr;
-    d.a_w_phase = cs.wphase_off >= 0 ? pk + cs.wphase_off : nullptr;
-    if (cs.ws_p >= 0) {
-      d.b0 = tptr(cs.sb0); d.b_c0 = u->tensors[cs.sb0].channels;
-      d.b1 = tptr(cs.sb1); d.b_c1 = cs.sb1 >= 0 ? u->tensors[cs.sb1].channels : 0;
-      d.b_w = pk + cs.wsk_off;
-    }
-    if (cs.bias_kind == 0) { d.bias = P(cs.bias_off); d.bias_bstride = 0; }
-    else { d.bias = ebias + cs.bias_off; d.bias_bstride = u->R; }
-    d.res = tptr(cs.res); d.res_mode = cs.rmode;
-    if (cs.out < 0) { d.out = out; d.out_dtype = CWDM_F32; }
-    else { d.out = wb + L.t_off[cs.out]; d.out_dtype = u->cfg.dtype; }
-    d.stats = (cs.stats && cs.out >= 0) ? reinterpret_cast<float*>(wb + L.s_off[cs.out]) : nullptr;
-    // this conv's context: the plan's zeroed sync block, per-workgroup statistics, the profiling hook
-    cwdm::ConvCall cc;
-    cc.sync = reinterpret_cast<unsigned*>(wb + L.sync);
-    cc.stats_wg = plan_stats_wg();
-    if (u->profiling) cc.prof = &u->hooks[conv_i];
-    const ConvPlan& cp = L.conv[st.idx];
-    ConvKind kind = keep ? cp.kind_keep : cp.kind;
-    if (kind == ConvKind::SkipTaken) {
-      // the skip was computed in conv1's GroupNorm pass: a plain residual here
-      d.b0 = d.b1 = nullptr; d.b_c0 = d.b_c1 = 0; d.b_w = nullptr;
-      d.res = wb + L.skipbuf; d.res_mode = 0;
-      kind = ConvKind::Plain;
-    }
-    // (the output head fuses the sampling step where the step's arguments allow: a run-time question)
-    const bool head_samp = kind != ConvKind::SkipPass && samp && cs.out < 0 && cwdm::head_sampler_eligible(&d, samp);
-    if (head_samp) {
-      if ((rc = flush_fin())) return rc;
-      if ((rc = cwdm::head_sampler_forward(&d, samp, cc.prof, s))) return rc;
-      if (fused) *fused = 1;
-    } else switch (kind) {
-      case ConvKind::SkipPass: {
-        // conv1 of a skip block: SiLU(GN1(x)) for this conv and W_skip . x for conv2 in one pass
-        const auto& c2 = u->convs[cs.skip_conv];
-        const int64_t vpb = d.D * d.H * d.W;
-        void* act = keep && L.keep_off[st.idx] >= 0 ? wb + L.keep_off[st.idx] : wb + L.split;
-        if ((rc = flush_fin())) return rc;
-        if ((rc = cwdm::gn_apply_skip(d.a0, d.a_c0, d.a1, d.a_c1, d.a_gn, B, vpb, u->cfg.dtype, pk + c2.wsk_off,
-                                      c2.cout, act, wb + L.skipbuf, s)))
-          return rc;
-        void* part = wb + L.split + cp.route.ws_act;   // (the K-split slices follow the activated input)
-        if ((rc = cwdm::v4_launch(&d, act, d.a_c0 + d.a_c1, nullptr, 0, 1, d.res, d.res_mode, part, cp.pass, cc, s)))
-          return rc;
-        break;
-      }
-      case ConvKind::HeadSplit: {
-        // the accurate fast mode's head: a bf16 head over the K-expanded split input (head_split3_prep)
-        if ((rc = flush_fin())) return rc;
-        void* x3 = wb + L.split;
-        if ((rc = cwdm::head_split3_prep(reinterpret_cast<const float*>(d.a0), d.a_gn, B, d.D * d.H * d.W, d.a_c0, x3,
-                                          s)))
-          return rc;
-        cwdm_conv3d_desc e = d;
-        e.dtype = CWDM_BF16;
-        e.a0 = x3; e.a_c0 = 3 * d.a_c0; e.a1 = nullptr; e.a_c1 = 0;
-        e.a_gn = nullptr; e.a_w = pk + cs.hsplit_off; e.a_w_split = nullptr;
-        e.workspace = nullptr; e.ws_bytes = 0;
-        if ((rc = cwdm::conv3d_forward(&e, cc, s))) return rc;
-        break;
-      }
-      case ConvKind::Xsg: {
-        // the accurate fast mode on a small grid: one bf16 small-grid conv over the K-expanded split input
-        const XsgPlan& xp = L.xsg[cp.xsg];
-        if ((rc = flush_fin())) return rc;
-        unsigned char* x3 = wb + L.split;
-        const void* res = d.res;
-        int rmode = d.res_mode;
-        cc.fp32x = true;
-        void* part = x3 + xp.x3_bytes + xp.skip_bytes;
-        if (d.b_w && xp.sk_sg) {
-          // the 1x1 skip first, into an fp32 residual: K-expanded split of the raw input on the small-grid kernel
-          if ((rc = cwdm::split3_prep(reinterpret_cast<const float*>(d.b0), d.b_c0, reinterpret_cast<const float*>(d.b1),
-                                      d.b_c1, nullptr, B, d.D * d.H * d.W, 0, x3, s)))
-            return rc;
-          cwdm_conv3d_desc k = xp.ek;
-          k.b0 = x3; k.b_w = pk + cs.xsplit_sk_off;
-          if ((rc = cwdm::sg_skip_launch(&k, x3 + xp.x3_bytes, xp.sk_ksplit > 1 ? part : nullptr, xp.sk_ksplit, cc, s)))
-            return rc;
-          res = x3 + xp.x3_bytes; rmode = 0;
-        } else if (d.b_w) {
-          // the 1x1 skip first, into an fp32 residual (pw_split: the split products of the 1x1 weights)
-          cwdm_conv3d_desc k = d;
-          k.a0 = k.a1 = nullptr; k.a_c0 = k.a_c1 = 0; k.a_gn = nullptr; k.a_w = nullptr; k.a_mode = 0;
-          k.bias = nullptr; k.bias_bstride = 0; k.stats = nullptr; k.res = nullptr; k.res_mode = -1;
-          k.out = x3 + xp.x3_bytes; k.out_dtype = CWDM_F32;
-          k.workspace = nullptr; k.ws_bytes = 0;
-          if ((rc = xp.sk_pw_split ? cwdm::pw_split_forward(&k, cc.prof, s) : cwdm::conv3d_forward(&k, cc, s)))
-            return rc;
-          res = k.out; rmode = 0;
-        }
-        const int64_t sv = cs.amode == 1 ? (d.D / 2) * (d.H / 2) * (d.W / 2) : d.D * d.H * d.W;
-        if ((rc = cwdm::split3_prep(reinterpret_cast<const float*>(d.a0), d.a_c0, reinterpret_cast<const float*>(d.a1),
-                                    d.a_c1, d.a_gn, B, sv, 1, x3, s)))
-          return rc;
-        cwdm_conv3d_desc e = xp.e;
-        e.a0 = x3; e.a1 = nullptr; e.a_w = pk + cs.xsplit_off;
-        e.bias = d.bias; e.bias_bstride = d.bias_bstride;
-        e.res = res; e.res_mode = rmode;
-        e.out = d.out; e.stats = d.stats;
-        e.workspace = nullptr; e.ws_bytes = 0;
-        if (xp.er.ksplit <= 1) part = nullptr;
-        if ((rc = cwdm::v4_launch(&e, x3, e.a_c0, nullptr, 0, 1, res, rmode, part, xp.er, cc, s))) return rc;
-        break;
-      }
-      default: {
-        cc.act_keep = keep && L.keep_off[st.idx] >= 0 ? wb + L.keep_off[st.idx] : nullptr;
-        cwdm::GnFinFuse ff{};
-        const bool offer = fin_pend >= 0 && d.a_gn == reinterpret_cast<const float*>(wb + L.ss_off[u->gns[fin_pend].ss_id]);
-        if (offer) {
-          fin_args(fin_pend, ff);
-          fin_pend = -1;
-          cc.gnfin = &ff;
-        } else if ((rc = flush_fin())) {
-          return rc;
-        }
-        if ((rc = cwdm::conv3d_forward(&d, cc, s))) return rc;
-        CWDM_REQUIRE(!offer || ff.used, CWDM_E_INVALID,
-                     "cwdm_unet_forward: conv " + std::to_string(st.idx) + " did not take its GroupNorm finalize");
-        CWDM_REQUIRE(!cc.act_keep || cc.act_kept, CWDM_E_INVALID,
-                     "cwdm_unet_forward: conv " + std::to_string(st.idx) + " did not keep its activated input");
-      }
-    }
-    if (cc.stats_rows > 0 && cs.out >= 0) srows[cs.out] = cc.stats_rows;
-    if (u->profiling) u->ev_used = conv_i + 1;
-    ++conv_i;
-  }
-  return flush_fin();
+  Forward fw{{u, L, reinterpret_cast<const unsigned char*>(packed), reinterpret_cast<unsigned char*>(ws), x, B, D, H, W,
+              stream}, out, t, keep, samp, fused};
+  if (int rc = fw.begin()) return rc;
+  return fw.run();
 }
 
 extern "C" int cwdm_unet_forward(cwdm_unet* u, const void* packed, const void* x, const float* t, float* out,
@@ -1571,11 +1627,11 @@ extern "C" int cwdm_unet_trace_count(const cwdm_unet* u) { return u ? (int)u->tr
 extern "C" int cwdm_unet_trace_info(const cwdm_unet* u, int i, int64_t B, int64_t D, int64_t H, int64_t W,
                                     int64_t* off, int* ch, int* level) {
   CWDM_REQUIRE(u && i >= 0 && i < (int)u->trace.size(), CWDM_E_INVALID, "cwdm_unet_trace_info: bad index");
-  const int id = u->trace[i];
+  const int id = u->trace[i].tensor;
   Layout L = layout(u, B, D, H, W);
   if (off) *off = id >= 0 ? L.t_off[id] : -1;
   if (ch) *ch = id >= 0 ? u->tensors[id].channels : u->cfg.out_channels;
-  if (level) *level = u->trace_level[i];
+  if (level) *level = u->trace[i].level;
   return CWDM_OK;
 }
 
@@ -1815,19 +1871,14 @@ struct GnBwdOpt {
 // GroupNorm backward's input), G.chs, G.gnws, G.wgws and G.split, so a segment's launch order is part of its
 // result.  The store / accumulate state of the gradient buffers (u->ginit, take_acc) lives in the plan: it
 // carries over between calls that each run a range of segments.
-struct Backward {
-  cwdm_unet* u;
-  const Layout& L;
+struct Backward : PlanView {
   const GLayout& G;
-  const unsigned char *pk, *pb, *wb;   // packed parameters (forward, backward form), the forward's workspace
-  unsigned char* gb;                   // the gradient workspace
-  const void* x; const float *t, *dout; float* grads;
-  int64_t B, D, H, W;
+  const unsigned char* pb;   // packed parameters, backward form
+  unsigned char* gb;         // the gradient workspace
+  const float *t, *dout; float* grads;
   bool kept;   // the forward ran on a training-sized workspace: the convs' activated inputs are there
-  cwdm_stream_t stream;
   // derived from the above
-  hipStream_t s = (hipStream_t)stream;
-  int dt = u->cfg.dtype, es = esize(dt);
+  int es = esize(dt);
   unsigned* sync = reinterpret_cast<unsigned*>(gb + G.sync);   // the zeroed sync block (ConvCall::sync)
   const float* temb = reinterpret_cast<const float*>(wb + L.temb);
   float* deb = reinterpret_cast<float*>(gb + G.deb);     // d emb projection rows [B][R]
@@ -1835,14 +1886,8 @@ struct Backward {
   void* tmp = gb + G.tmp;
   float* gbp = reinterpret_cast<float*>(gb + G.gbp);
 
-  const float* P(int64_t off) const { return reinterpret_cast<const float*>(pk + off); }
   float* GR(int pi) const { return grads + u->goff[pi]; }
-  const void* act(int id) const { return id < 0 ? nullptr : (id == u->input_tensor ? x : wb + L.t_off[id]); }
   void* grd(int id) const { return id < 0 ? nullptr : gb + G.g_off[id]; }
-  int nch(int id) const { return id < 0 ? 0 : u->tensors[id].channels; }
-  int64_t vox(int lv) const { return (D >> lv) * (H >> lv) * (W >> lv); }
-  const float* ss_of(int g) const { return reinterpret_cast<const float*>(wb + L.ss_off[g]); }
-  const float* mr_of(int g) const { return reinterpret_cast<const float*>(wb + L.mr_off[g]); }
   // first writer stores, later writers accumulate
   int take_acc(int id) { return id < 0 ? 0 : (std::exchange(u->ginit[id], char(1)) ? 1 : 0); }
 
@@ -2258,9 +2303,9 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
   CWDM_REQUIRE(seg_begin == 0 || (int)u->ginit.size() == (int)u->tensors.size(), CWDM_E_INVALID,
                "cwdm_unet_backward: segment 0 must run first");
   using UC = unsigned char;
-  Backward bw{u, L, G, reinterpret_cast<const UC*>(packed), reinterpret_cast<const UC*>(packed_bwd),
-              reinterpret_cast<const UC*>(ws), reinterpret_cast<UC*>(gws), x, t, dout, grads, B, D, H, W,
-              L.train_total > L.total && ws_bytes >= L.train_total, stream};
+  Backward bw{{u, L, reinterpret_cast<const UC*>(packed), static_cast<UC*>(const_cast<void*>(ws)), x, B, D, H, W, stream},
+              G, reinterpret_cast<const UC*>(packed_bwd), reinterpret_cast<UC*>(gws), t, dout, grads,
+              L.train_total > L.total && ws_bytes >= L.train_total};
   // (every call: a caller may run segments on a fresh grad workspace)
   CWDM_HIP(hipMemsetAsync(bw.sync, 0, cwdm::plan_sync_bytes(), bw.s));
   // segment 0 the output head, then the blocks last to first, then conv_in + time_embed
