@@ -51,7 +51,7 @@ __device__ __forceinline__ void pack_elem(const float* __restrict__ w, int cout,
   if (co < cout && ci < cin_real) {
     if (s2_ci0) v = transpose ? s2_weight(w, s2_ci0, ci, co, ntaps - 1 - tap) : s2_weight(w, s2_ci0, co, ci, tap);
     else if (transpose) v = w[((long long)ci * cout + co) * ntaps + (ntaps - 1 - tap)];
-    else v = w[((long long)co * cin + ci) * ntaps + tap];
+    else v = w[((long long)co * cin_real + ci) * ntaps + tap];   // (cin_real < cin: pack_zext_job's zero columns)
   }
   out[i] = Elem<T>::from_f(v);
 }
@@ -337,6 +337,13 @@ int pack_job(const float* w, int cout, int cin, int ksize, int dtype, void* pack
   return pack_job_impl(w, cout, cin, ksize, dtype, packed, 0, 0, j);
 }
 
+int pack_zext_job(const float* w, int cout, int cin_real, int cin, int dtype, void* packed, PackJob& j) {
+  CWDM_REQUIRE(cin_real > 0 && cin_real <= cin, CWDM_E_INVALID, "cwdm_conv3d_pack: bad zero extension");
+  if (int rc = pack_job_impl(w, cout, cin, 3, dtype, packed, 0, 0, j)) return rc;
+  j.cin_real = cin_real;
+  return CWDM_OK;
+}
+
 int pack_s2_job(const float* w, int cout, int cin, int dtype, void* packed, int transpose, PackJob& j) {
   // forward: a (cout -> 8 cin) conv over the space-to-depth input; transpose: its dgrad (8 cin outputs)
   return transpose ? pack_job_impl(w, 8 * cin, cout, 3, dtype, packed, 1, cin, j)
@@ -419,7 +426,8 @@ int pack_batch_run(std::vector<PackJob>& jobs, int dtype, PackJob* table, std::v
   // the tiled kernel's jobs (no stride-2 fold, ntaps <= 27) first, then the gather kernel's
   static const bool tiled_on = env_not0("CWDM_PACK_TILED");
   auto tiled = [&](const PackJob& j) {
-    return tiled_on && j.s2_ci0 == 0 && !j.phase && j.ntaps <= 27 && j.NT % 32 == 0;
+    return tiled_on && j.s2_ci0 == 0 && !j.phase && j.ntaps <= 27 && j.NT % 32 == 0 &&
+           (j.transpose || j.cin_real == j.cin);   // (a zero-extended job: the gather kernel)
   };
   std::stable_partition(jobs.begin(), jobs.end(), tiled);
   size_t nt = 0;

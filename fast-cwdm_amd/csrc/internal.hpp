@@ -99,6 +99,9 @@ constexpr int kV5AaWords = 4096;   // apply-ahead sweep counters of one launch (
 // checks and error codes; a caller batches its jobs through pack_batch_run)
 int legacy_conv3d_forward(const cwdm_conv3d_desc* d, ProfHook* prof, hipStream_t s);
 int pack_job(const float* w, int cout, int cin, int ksize, int dtype, void* packed, PackJob& j);
+// a 3x3x3 conv whose packed input channels [cin_real, cin) are zero columns (w is cout x cin_real OIDHW): the
+// U-Net's conv_in over an input padded to the K chunk
+int pack_zext_job(const float* w, int cout, int cin_real, int cin, int dtype, void* packed, PackJob& j);
 int pack_s2_job(const float* w, int cout, int cin, int dtype, void* packed, int transpose, PackJob& j);
 int pack_dgrad_job(const float* w, int cout, int cin, int ksize, int dtype, void* packed, PackJob& j);
 int pack_phase_job(const float* w, int cout, int cin, int dtype, void* packed, PackJob& j);
@@ -146,6 +149,9 @@ int64_t plan_sync_bytes();
 unsigned* plan_aa_counters(unsigned* sync);
 
 // ---- what else the U-Net plan drives --------------------------------------
+// layout.hip: dst (voxels, c_dst) = [src (voxels, c_src) | zeros], channels-last, both 16-byte aligned with whole
+// 16-byte quads of channels; every lane of dst is written on every call
+int pad_channels(const void* src, int c_src, void* dst, int c_dst, int dtype, int64_t voxels, hipStream_t s);
 // embed.hip
 int launch_time_embed(const float* t, int B, int mc, const float* w1, const float* b1, const float* w2,
                       const float* b2, float* temb, hipStream_t s);

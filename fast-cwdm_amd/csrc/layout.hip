@@ -1,7 +1,13 @@
 // Strided (b, c, v) copy with dtype conversion, tiled through LDS so that
 // both the channel-planar (NCDHW) and the channels-last (NDHWC) side are
 // accessed with consecutive lanes on consecutive addresses.
+//
+// pad_channels: a channels-last tensor copied into a wider one whose extra channels are zero (the U-Net
+// plan's staged input).
+#include <cstdint>
+
 #include "common.hpp"
+#include "internal.hpp"
 
 namespace cwdm {
 namespace {
@@ -65,7 +71,53 @@ int launch_dst(const void* src, const int64_t* s, void* dst, int ddt, const int6
   return CWDM_OK;
 }
 
+// dst (n voxels, dq 16-byte quads each) = src (n voxels, sq quads each) followed by zero quads: a thread per
+// output quad, consecutive lanes on consecutive addresses of both sides
+__global__ void __launch_bounds__(256) pad_channels_kernel(const uint4* __restrict__ src, int sq,
+                                                          uint4* __restrict__ dst, int dq, FastDiv dqd,
+                                                          long long total) {
+  const long long i0 = (long long)blockIdx.x * 1024 + threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {   // 4 independent loads in flight per lane
+    const long long i = i0 + k * 256;
+    if (i >= total) return;
+    // (voxel, quad) of output quad i (fdiv is exact below 2^31)
+    long long v;
+    int q;
+    if (i < (1LL << 31)) {
+      const unsigned vq = fdiv((unsigned)i, dqd);
+      v = vq;
+      q = (int)((unsigned)i - vq * (unsigned)dq);
+    } else {
+      v = i / dq;
+      q = (int)(i - v * dq);
+    }
+    uint4 x = make_uint4(0u, 0u, 0u, 0u);
+    if (q < sq) x = src[v * sq + q];
+    dst[i] = x;
+  }
+}
+
 }  // namespace
+
+int pad_channels(const void* src, int c_src, void* dst, int c_dst, int dtype, int64_t voxels, hipStream_t s) {
+  CWDM_REQUIRE(src && dst, CWDM_E_INVALID, "pad_channels: null pointer");
+  const int epq = 16 / dtype_size(dtype);
+  CWDM_REQUIRE(c_src > 0 && c_src <= c_dst && c_src % epq == 0 && c_dst % epq == 0, CWDM_E_UNSUPPORTED,
+               "pad_channels: channel counts must be whole 16-byte quads");
+  CWDM_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 15) == 0, CWDM_E_INVALID,
+               "pad_channels: tensors must be 16-byte aligned");
+  if (voxels <= 0) return CWDM_OK;
+  const int sq = c_src / epq, dq = c_dst / epq;
+  const long long total = voxels * dq;
+  const long long blocks = ceil_div(total, 1024);
+  CWDM_REQUIRE(blocks < (1LL << 31), CWDM_E_UNSUPPORTED, "pad_channels: grid too large");
+  hipLaunchKernelGGL(pad_channels_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
+                     reinterpret_cast<const uint4*>(src), sq, reinterpret_cast<uint4*>(dst), dq, make_fastdiv(dq),
+                     total);
+  CWDM_LAUNCHED();
+  return CWDM_OK;
+}
 }  // namespace cwdm
 
 using namespace cwdm;

@@ -73,6 +73,9 @@ struct ConvStep {
   int64_t xsplit_off = -1;      // accurate fast mode, small grids (level >= 2): the same for the bf16 small-grid kernel
   int64_t xsplit_sk_off = -1;   //   and for its 1x1 skip (k = 1)
   int s2 = 0;                   // stride-2 conv (Downsample.op) over a space-to-depth input: cin_a = 8 x its channels
+  int cin_w = 0;                // conv_in over the staged input: the weight's own input channels (< cin_a: the packed
+                                // columns past them are zero), 0: cin_a
+  int w_cin() const { return cin_w ? cin_w : cin_a; }
 };
 
 struct S2dStep {  // space-to-depth of a Downsample conv's input (stride2.hip)
@@ -112,7 +115,7 @@ struct AttnStep {
 };
 
 enum StepKind { kGn, kConv, kPool /* pre-pass */, kS2d /* space-to-depth */, kHaar, kAvg /* additive skip */,
-                kAttn /* bottleneck attention */, kDrop /* out_layers dropout */ };
+                kAttn /* bottleneck attention */, kDrop /* out_layers dropout */, kStage /* zero-padded input */ };
 struct Step { StepKind kind; int idx; };
 
 // what one Block is: the backward runs one function per kind (struct Backward)
@@ -188,6 +191,8 @@ struct cwdm_unet {
   struct Trace { int tensor, level; };
   std::vector<Trace> trace;       // per topology block: its output tensor (-1 = final output) and level
   int input_tensor = -1;          // pseudo tensor for x
+  int stage_tensor = -1;          // in_channels no multiple of the K chunk: x zero-padded to it (the kStage step
+                                  // writes every lane on every forward), conv_in's input; -1: conv_in reads x
   int R = 0;                      // emb projection rows
   std::vector<int> emb_rows_w, emb_rows_b, emb_rows_cb;  // per res block: emb weight/bias param, conv1 bias param
                                                          // (-1: the conv bias is not folded, WavUNet up/down)
@@ -260,7 +265,19 @@ void build(cwdm_unet* u) {
   {
     ConvStep cs{};
     conv_params("input_blocks.0.0", mc, c.in_channels, 3, &cs.w_p, &cs.b_p);
-    cs.a0 = u->input_tensor; cs.a1 = -1; cs.amode = 0; cs.gn = -1; cs.cin_a = c.in_channels;
+    cs.a0 = u->input_tensor; cs.cin_a = c.in_channels;
+    // 8 + 8x input channels on 16-channel K chunks: the conv runs over a zero-padded copy of x with zero
+    // weight columns (the parameter keeps the model's shape; use_freq plans are aligned, cwdm_unet_create)
+    const int ck = ck_of(c.dtype);
+    if (c.in_channels % ck) {
+      cs.cin_w = c.in_channels;
+      cs.cin_a = (c.in_channels + ck - 1) / ck * ck;
+      cs.a0 = u->stage_tensor = new_tensor(0, cs.cin_a);
+      u->tensors[cs.a0].stats_kind = -1;
+      u->tensors[cs.a0].grad = false;
+      u->steps.push_back({kStage, 0});
+    }
+    cs.a1 = -1; cs.amode = 0; cs.gn = -1;
     cs.sb0 = cs.sb1 = -1; cs.ws_p = cs.wsb_p = -1; cs.cin_b = 0;
     cs.bias_kind = 0; cs.res = -1; cs.rmode = -1;
     cs.cout = mc; cs.level = 0; cs.stats = true;
@@ -1028,8 +1045,11 @@ extern "C" int cwdm_unet_create(const cwdm_unet_config* cfg, cwdm_unet** plan) {
   CWDM_REQUIRE(dtype_compute(cfg->dtype), CWDM_E_INVALID, "cwdm_unet_create: bad dtype");
   CWDM_REQUIRE(cfg->num_groups > 0, CWDM_E_INVALID, "cwdm_unet_create: bad num_groups");
   const int ck = ck_of(cfg->dtype);
-  CWDM_REQUIRE(cfg->in_channels % ck == 0, CWDM_E_UNSUPPORTED,
-               "cwdm_unet_create: in_channels must be a multiple of " + std::to_string(ck));
+  // 8 wavelet channels per volume (the image and each condition); a UNetModel plan pads them to the K chunk
+  // itself (stage_tensor), WavUNetModel's pyramid reads the input tensor as it is
+  CWDM_REQUIRE(cfg->in_channels % 8 == 0, CWDM_E_UNSUPPORTED, "cwdm_unet_create: in_channels must be a multiple of 8");
+  CWDM_REQUIRE(!cfg->use_freq || cfg->in_channels % ck == 0, CWDM_E_UNSUPPORTED,
+               "cwdm_unet_create: use_freq: in_channels must be a multiple of " + std::to_string(ck));
   for (int l = 0; l < cfg->num_levels; ++l) {
     const int ch = cfg->channel_mult[l] * cfg->model_channels;
     CWDM_REQUIRE(ch > 0 && ch % ck == 0 && (ch % 64 == 0 || ch % 32 == 0), CWDM_E_UNSUPPORTED,
@@ -1189,8 +1209,9 @@ extern "C" int cwdm_unet_pack(const cwdm_unet* uc, const float* const* P, void* 
   cwdm::PackJob j;
   int rc;
   for (const auto& cs : u->convs) {
-    if ((rc = cs.s2 ? cwdm::pack_s2_job(P[cs.w_p], cs.cout, cs.cin_a / 8, u->cfg.dtype, base + cs.w_off, 0, j)
-                    : cwdm::pack_job(P[cs.w_p], cs.cout, cs.cin_a, 3, u->cfg.dtype, base + cs.w_off, j)))
+    if ((rc = cs.s2      ? cwdm::pack_s2_job(P[cs.w_p], cs.cout, cs.cin_a / 8, u->cfg.dtype, base + cs.w_off, 0, j)
+              : cs.cin_w ? cwdm::pack_zext_job(P[cs.w_p], cs.cout, cs.cin_w, cs.cin_a, u->cfg.dtype, base + cs.w_off, j)
+                         : cwdm::pack_job(P[cs.w_p], cs.cout, cs.cin_a, 3, u->cfg.dtype, base + cs.w_off, j)))
       return rc;
     jobs.push_back(j);
     if (cs.wphase_off >= 0) {
@@ -1256,7 +1277,8 @@ extern "C" double cwdm_unet_flops(const cwdm_unet* u, int64_t B, int64_t D, int6
   double f = 0;
   for (const auto& cs : u->convs) {
     const double v = (double)B * (D >> cs.level) * (H >> cs.level) * (W >> cs.level);
-    f += 2.0 * v * cs.cout * (27.0 * (cs.s2 ? cs.cin_a / 8 : cs.cin_a) + cs.cin_b);  // algorithmic (stride-2: 27 C taps)
+    // algorithmic (stride-2: 27 C taps; conv_in: the model's input channels, not the padded ones)
+    f += 2.0 * v * cs.cout * (27.0 * (cs.s2 ? cs.cin_a / 8 : cs.w_cin()) + cs.cin_b);
   }
   for (const auto& at : u->attns) {   // the qkv and proj GEMMs, q k^T and P v
     const double T = (double)(D >> at.level) * (H >> at.level) * (W >> at.level);
@@ -1344,6 +1366,7 @@ struct Forward : PlanView {
         case kAvg: rc = avg(u->avgs[st.idx]); break;
         case kAttn: rc = attention(u->attns[st.idx]); break;
         case kDrop: rc = dropout(u->drops[st.idx]); break;
+        case kStage: rc = stage(); break;
       }
       if (rc) return rc;
     }
@@ -1396,6 +1419,11 @@ struct Forward : PlanView {
   }
 
   // ---- the steps that are one launch (dropout and attention read a norm no conv takes: run() flushed it)
+  // x, dense (B, D, H, W, in_channels), into its zero-padded copy: real zeros in the padded lanes whatever the
+  // workspace held (the backward's weight gradient reads the copy too)
+  int stage() {
+    return cwdm::pad_channels(x, u->cfg.in_channels, dst(u->stage_tensor), nch(u->stage_tensor), dt, B * vox(0), s);
+  }
   int pool(const PoolStep& ps) {
     const int lv = ps.level_out;
     return cwdm_gn_silu_pool(act(ps.src), ps.channels, ss_of(ps.ss_id), B, D >> lv, H >> lv, W >> lv, dt,
@@ -1710,6 +1738,23 @@ cwdm_conv3d_desc dgrad_shape(const cwdm_unet* u, int i, int64_t B, int64_t D, in
   return d;
 }
 
+// conv_in's weight gradient where its input channels are no multiple of the wgrad kernels' 32 (8 + 8x channels) or
+// are padded ones: the input padded to 32s, then the gradient over the padded columns, both in the dgrads' scratch
+// tmp, which is free by the last segment (Backward::stem copies the real columns out)
+struct StemPad {
+  int cw = 0;   // the wgrad's input channels, 0: conv_in's wgrad writes the parameter's gradient directly
+  int64_t x_bytes = 0, dw_bytes = 0;
+};
+StemPad stem_pad(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) {
+  const auto& c0 = u->convs[0];
+  StemPad p;
+  if (c0.cin_a % 32 == 0 && !c0.cin_w) return p;
+  p.cw = (c0.cin_a + 31) / 32 * 32;
+  p.x_bytes = p.cw == c0.cin_a ? 0 : align_up(B * D * H * W * p.cw * esize(u->cfg.dtype));
+  p.dw_bytes = (int64_t)c0.cout * p.cw * 27 * 4;
+  return p;
+}
+
 GLayout glayout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) {
   GLayout G;
   int64_t off = 0;
@@ -1737,6 +1782,10 @@ GLayout glayout(const cwdm_unet* u, int64_t B, int64_t D, int64_t H, int64_t W) 
   for (const auto& g : u->gns) {
     const int lv = g.level;
     gnws = std::max(gnws, cwdm_gn_silu_bwd_workspace_bytes(g.channels, B, D >> lv, H >> lv, W >> lv));
+  }
+  if (const StemPad sp = stem_pad(u, B, D, H, W); sp.cw) {
+    tmp = std::max(tmp, sp.x_bytes + sp.dw_bytes);
+    wgws = std::max(wgws, cwdm_conv3d_wgrad_workspace_bytes(u->convs[0].cout, sp.cw, 3));
   }
   G.tmp = take(tmp);
   G.dout = take(B * D * H * W * ckpad(u, u->cfg.out_channels) * es);
@@ -1848,7 +1897,7 @@ extern "C" double cwdm_unet_backward_flops(const cwdm_unet* u, int64_t B, int64_
   for (size_t i = 0; i < u->convs.size(); ++i) {
     const auto& cs = u->convs[i];
     const double v = (double)B * (D >> cs.level) * (H >> cs.level) * (W >> cs.level);
-    const double fwd = 2.0 * v * cs.cout * (27.0 * (cs.s2 ? cs.cin_a / 8 : cs.cin_a) + cs.cin_b);
+    const double fwd = 2.0 * v * cs.cout * (27.0 * (cs.s2 ? cs.cin_a / 8 : cs.w_cin()) + cs.cin_b);
     f += i == 0 ? fwd : 2 * fwd;  // wgrad (+ dgrad)
   }
   return f;
@@ -2270,11 +2319,31 @@ struct Backward : PlanView {
   }
 
   // ---- the last segment: conv_in + time_embed
+  // conv_in's weight gradient: of the model's own input channels only, whatever the kernels ran on (StemPad)
+  int stem_wgrad() {
+    const auto& c0 = u->convs[0];
+    const void* xin = act(c0.a0);   // x, or the forward's staged copy
+    const StemPad sp = stem_pad(u, B, D, H, W);
+    if (!sp.cw) return wgrad(0, 3, xin, c0.cin_a, nullptr, 0, 0, nullptr, grd(c0.out), c0.cout, c0.cout, GR(c0.w_p));
+    int rc;
+    unsigned char* scratch = reinterpret_cast<unsigned char*>(tmp);
+    if (sp.x_bytes) {
+      if ((rc = cwdm::pad_channels(xin, c0.cin_a, scratch, sp.cw, dt, B * vox(0), s))) return rc;
+      xin = scratch;
+    }
+    float* dwp = reinterpret_cast<float*>(scratch + sp.x_bytes);
+    CWDM_HIP(hipMemsetAsync(dwp, 0, sp.dw_bytes, s));
+    if ((rc = wgrad(0, 3, xin, sp.cw, nullptr, 0, 0, nullptr, grd(c0.out), c0.cout, c0.cout, dwp))) return rc;
+    // dw[co][ci][tap] for ci < the parameter's input channels (the rest: zero inputs' columns, dropped)
+    const int ci = c0.w_cin();
+    const int64_t ss_[3] = {(int64_t)sp.cw * 27, 27, 1}, ds_[3] = {(int64_t)ci * 27, 27, 1};
+    return cwdm_copy3(dwp, CWDM_F32, ss_, GR(c0.w_p), CWDM_F32, ds_, c0.cout, ci, 27, stream);
+  }
   int stem() {
     const auto& c0 = u->convs[0];
     int rc;
     if ((rc = bias_grad(grd(c0.out), 0, c0.cout, GR(c0.b_p)))) return rc;
-    if ((rc = wgrad(0, 3, x, c0.cin_a, nullptr, 0, 0, nullptr, grd(c0.out), c0.cout, c0.cout, GR(c0.w_p)))) return rc;
+    if ((rc = stem_wgrad())) return rc;
     return launch_temb_bwd(t, (int)B, u->cfg.model_channels, P(u->off_te_w1), P(u->off_te_b1), P(u->off_te_w2), temb,
                            dsil, GR(u->te_w1), GR(u->te_b1), GR(u->te_w2), GR(u->te_b2), s);
   }

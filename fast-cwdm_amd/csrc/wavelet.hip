@@ -175,6 +175,71 @@ __global__ void __launch_bounds__(256) prepare_batch_kernel(PrepArgs a) {
   }
 }
 
+// The same front end for 0..7 condition volumes (cwdm_prepare_batch_n): the model input is
+// [x_t | cond 0 | ... | cond ncond-1], 8 + 8 ncond channels.  The volume pointers travel by value in the
+// kernel arguments; every value is computed by the expressions of prepare_batch_kernel, so ncond = 3
+// reproduces it bit for bit.
+struct PrepNArgs {
+  const float* target;
+  const float* eps;
+  const float* cond[7];
+  int ncond;
+  float* x_in;           // (B, 8 + 8 ncond, d, h, w)
+  float* x0;             // (B, 8, d, h, w)
+  const float* coef;     // as PrepArgs
+  const int64_t* t;
+  int64_t T, B, d, h, w;
+  int per_band;
+};
+
+// Haar analysis of the 2x2x2 block at base (row stride W, plane stride H W)
+__device__ __forceinline__ void prep_bands(const float* base, int64_t H, int64_t W, float* bands) {
+  float blk[8];
+#pragma unroll
+  for (int aa = 0; aa < 2; ++aa)
+#pragma unroll
+    for (int bb = 0; bb < 2; ++bb) {
+      const float2 p = *reinterpret_cast<const float2*>(base + (aa * H + bb) * W);
+      blk[aa * 4 + bb * 2 + 0] = p.x;
+      blk[aa * 4 + bb * 2 + 1] = p.y;
+    }
+  haar_fwd8(blk, bands);
+}
+
+__global__ void __launch_bounds__(256) prepare_batch_n_kernel(PrepNArgs a) {
+  const int64_t nvox = a.d * a.h * a.w;
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= a.B * nvox) return;
+  const int64_t b = idx / nvox, v = idx - b * nvox;
+  const int64_t k = v % a.w, j = (v / a.w) % a.h, i = v / (a.w * a.h);
+  const int64_t W = 2 * a.w, H = 2 * a.h;
+  const int64_t in_off = b * (nvox * 8) + ((2 * i) * H + 2 * j) * W + 2 * k;
+  float tg[8], ep[8];
+  prep_bands(a.target + in_off, H, W, tg);
+  tg[0] = __fdiv_rn(tg[0], 3.0f);
+  prep_bands(a.eps + in_off, H, W, ep);
+  int64_t t = a.t[b];
+  t = t < 0 ? 0 : (t >= a.T ? a.T - 1 : t);
+  const float* cq = a.coef + t * (a.per_band ? 16 : 2);
+  const int bs = a.per_band ? 2 : 0;
+  float* xin = a.x_in + b * (8 + 8 * a.ncond) * nvox + v;
+  float* x0 = a.x0 + b * 8 * nvox + v;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    x0[q * nvox] = tg[q];
+    xin[q * nvox] = ad(mr(cq[q * bs], tg[q]), mr(cq[q * bs + 1], ep[q]));
+  }
+#pragma unroll   // (static indices into the by-value pointer array)
+  for (int s = 0; s < 7; ++s) {
+    if (s >= a.ncond) break;
+    float cb[8];
+    prep_bands(a.cond[s] + in_off, H, W, cb);
+    cb[0] = __fdiv_rn(cb[0], 3.0f);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) xin[(8 * (s + 1) + q) * nvox] = cb[q];
+  }
+}
+
 struct S3 { int64_t b, c, v; };
 inline S3 s3(const int64_t* p) { return p ? S3{p[0], p[1], p[2]} : S3{0, 0, 0}; }
 
@@ -341,6 +406,31 @@ extern "C" int cwdm_prepare_batch(const float* target, const float* c1, const fl
     CWDM_REQUIRE(((uintptr_t)a.img[s] & 7) == 0, CWDM_E_INVALID, "cwdm_prepare_batch: volumes must be 8-byte aligned");
   const int64_t n = B * a.d * a.h * a.w;
   hipLaunchKernelGGL(prepare_batch_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, a);
+  CWDM_LAUNCHED();
+  return CWDM_OK;
+}
+
+extern "C" int cwdm_prepare_batch_n(const float* target, const float* const* conds, int ncond, const float* eps_img,
+                                    int64_t B, int64_t D, int64_t H, int64_t W, const float* coef, int per_band,
+                                    const int64_t* t, int64_t T, float* x_in, float* x0, cwdm_stream_t stream) {
+  CWDM_REQUIRE(ncond >= 0 && ncond <= 7, CWDM_E_UNSUPPORTED, "cwdm_prepare_batch_n: 0..7 condition volumes");
+  CWDM_REQUIRE(target && eps_img && coef && t && x_in && x0 && (conds || ncond == 0), CWDM_E_INVALID,
+               "cwdm_prepare_batch_n: null pointer");
+  CWDM_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && T > 0, CWDM_E_SHAPE, "cwdm_prepare_batch_n: empty shape");
+  CWDM_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, CWDM_E_SHAPE, "cwdm_prepare_batch_n: D, H, W must be even");
+  PrepNArgs a{};
+  a.target = target; a.eps = eps_img; a.ncond = ncond;
+  a.x_in = x_in; a.x0 = x0; a.coef = coef; a.t = t;
+  a.T = T; a.B = B; a.d = D / 2; a.h = H / 2; a.w = W / 2; a.per_band = per_band ? 1 : 0;
+  uintptr_t bits = (uintptr_t)target | (uintptr_t)eps_img;
+  for (int s = 0; s < ncond; ++s) {
+    CWDM_REQUIRE(conds[s], CWDM_E_INVALID, "cwdm_prepare_batch_n: null condition volume");
+    a.cond[s] = conds[s];
+    bits |= (uintptr_t)conds[s];
+  }
+  CWDM_REQUIRE((bits & 7) == 0, CWDM_E_INVALID, "cwdm_prepare_batch_n: volumes must be 8-byte aligned");
+  const int64_t n = B * a.d * a.h * a.w;
+  hipLaunchKernelGGL(prepare_batch_n_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, a);
   CWDM_LAUNCHED();
   return CWDM_OK;
 }

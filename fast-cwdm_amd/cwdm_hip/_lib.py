@@ -156,6 +156,8 @@ _PROTOS = {
                                                i64, i64, vp, vp]),
     "cwdm_prepare_batch": (ctypes.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, ctypes.c_int, vp, i64, vp, vp,
                                           vp]),
+    "cwdm_prepare_batch_n": (ctypes.c_int, [vp, ctypes.POINTER(vp), ctypes.c_int, vp, i64, i64, i64, i64, vp,
+                                            ctypes.c_int, vp, i64, vp, vp, vp]),
     "cwdm_prepare_batch2": (ctypes.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, ctypes.c_int, vp, i64, vp, vp,
                                            vp]),
     "cwdm_sampler_step": (ctypes.c_int, [ctypes.POINTER(SamplerArgs), vp]),

@@ -115,6 +115,27 @@ def prepare_batch(target, c1, c2, c3, eps_img, coef, t, T, per_band=False):
     return x_in, x0
 
 
+def prepare_batch_n(target, conds, eps_img, coef, t, T, per_band=False):
+    """The same front end for 0..7 condition volumes (cwdm_prepare_batch_n): returns
+    (x_in (B, 8 + 8 len(conds), d, h, w) = [q_sample | the condition DWTs in the order given],
+    x0 (B, 8, d, h, w)).  Three conditions give prepare_batch's bits."""
+    conds = list(conds)   # (more than 7: the library refuses)
+    vols = [v.contiguous().float() for v in (target, *conds, eps_img)]
+    _need_cuda(*vols, coef, t)
+    for v in vols:
+        if v.dim() != 5 or v.shape[1] != 1 or v.shape != vols[0].shape:
+            raise AssertionError("prepare_batch_n: (B, 1, D, H, W) volumes of one shape")
+    B, _, D, H, W = vols[0].shape
+    n = len(conds)
+    x_in = torch.empty((B, 8 + 8 * n, D // 2, H // 2, W // 2), device=vols[0].device, dtype=torch.float32)
+    x0 = torch.empty((B, 8, D // 2, H // 2, W // 2), device=vols[0].device, dtype=torch.float32)
+    t = t.to(dtype=torch.int64).contiguous()
+    arr = (ctypes.c_void_p * max(n, 1))(*[v.data_ptr() for v in vols[1:-1]])
+    check(lib().cwdm_prepare_batch_n(_p(vols[0]), arr, n, _p(vols[-1]), B, D, H, W, _p(coef), 1 if per_band else 0,
+                                     _p(t), T, _p(x_in), _p(x0), _stream()), "training_losses")
+    return x_in, x0
+
+
 def prepare_batch2(target, c1, c2, c3, eps_img, coef, t, T, per_band=False):
     """The 2-level (config 5) training front end in one kernel
     (cwdm_prepare_batch2): returns (x_in (B, 256, d, h, w) = [q_sample |

@@ -555,21 +555,56 @@ class GaussianDiffusion:
     # ---- training -----------------------------------------------------------
     def training_losses(self, model, x_start, t, classifier=None, model_kwargs=None, noise=None, labels=None,
                         mode="default", contr="t1n"):
-        """i2i training loss (reference :1084-1166): returns
+        """Training loss (reference :1084-1166): returns
         (terms{"mse_wav": [8]}, model_output, model_output_idwt); with
         wavelet_levels = 2 the same on the 64-channel representation
-        (terms{"mse_wav": [64]}, config 5)."""
+        (terms{"mse_wav": [64]}, config 5).
+
+        mode='i2i', ``x_start`` a dict of the four BraTS modalities: the reference's
+        path, ``contr`` the target and the other three the conditions.
+
+        mode='i2i', ``x_start`` = {"target": vol, "cond": [vol, ...]} with 0..7
+        condition volumes (an extension, like ``noise_fn``; ``contr`` is ignored): the
+        reference's family of 8 + 8x input channels (run.sh:65), the model input
+        [q_sample(DWT(target)) | DWT(cond 0) | ...] from one kernel
+        (cwdm_prepare_batch_n).
+
+        mode='default', ``x_start`` a (B, 1, D, H, W) tensor: the unconditional model
+        (train.py's own defaults, in_channels=8) -- the target is ``x_start``, the
+        model input its 8 noisy subbands.  By specification: the reference declares
+        and defaults this mode but never binds ``target`` in it (:1139 raises
+        UnboundLocalError), so this is the i2i loss with no condition.
+
+        The model must take 8 + 8 len(cond) input channels (AssertionError)."""
         if model_kwargs is None:
             model_kwargs = {}
-        if mode != "i2i":
-            raise NotImplementedError("training_losses: only mode='i2i' is on the fast-cwdm path")
-        order = {"t1n": ("t1n", "t1c", "t2w", "t2f"), "t1c": ("t1c", "t1n", "t2w", "t2f"),
-                 "t2w": ("t2w", "t1n", "t1c", "t2f"), "t2f": ("t2f", "t1n", "t1c", "t2w")}
-        if contr not in order:
-            raise ValueError("This contrast can't be synthesized.")
-        keys = order[contr]
-        target = x_start[keys[0]]
-        ops._need_cuda(target)
+        if mode not in ("i2i", "default"):
+            raise NotImplementedError(f"training_losses: mode={mode!r} is not on the fast-cwdm path "
+                                      f"('i2i' and 'default' are)")
+        brats = False
+        if mode == "default":
+            if not th.is_tensor(x_start):
+                raise AssertionError("training_losses(mode='default'): x_start is a (B, 1, D, H, W) tensor")
+            target, conds = x_start, []
+        elif "target" in x_start:
+            target, conds = x_start["target"], list(x_start.get("cond", ()))
+        else:
+            order = {"t1n": ("t1n", "t1c", "t2w", "t2f"), "t1c": ("t1c", "t1n", "t2w", "t2f"),
+                     "t2w": ("t2w", "t1n", "t1c", "t2f"), "t2f": ("t2f", "t1n", "t1c", "t2w")}
+            if contr not in order:
+                raise ValueError("This contrast can't be synthesized.")
+            keys = order[contr]
+            target, conds = x_start[keys[0]], [x_start[k] for k in keys[1:]]
+            brats = True
+        ops._need_cuda(target, *conds)
+        if not brats:
+            if self.wavelet_levels == 2:
+                raise NotImplementedError("training_losses: wavelet_levels == 2 (cwdm_prepare_batch2) takes the "
+                                          "four BraTS modalities only: three conditions, not "
+                                          f"{len(conds)} (mode={mode!r})")
+            cin = getattr(getattr(model, "model", model), "in_channels", None)
+            if cin is not None and cin != 8 + 8 * len(conds):
+                raise AssertionError(f"model expects {cin} input channels, got 8 + {8 * len(conds)}")
         B, _, D, H, W = target.shape
         d, h, w = D // 2, H // 2, W // 2
         V = d * h * w
@@ -579,8 +614,7 @@ class GaussianDiffusion:
         if self.wavelet_levels == 2:
             # config 5 (no reference code; the levels-1 loss below restated on
             # the 64-channel block representation, oracle.diffusion.training_losses)
-            x_in, x_start_dwt = ops.prepare_batch2(target, x_start[keys[1]], x_start[keys[2]], x_start[keys[3]],
-                                                   noise_img, self.q_coef_table(dev), t, self.num_timesteps,
+            x_in, x_start_dwt = ops.prepare_batch2(target, *conds, noise_img, self.q_coef_table(dev), t, self.num_timesteps,
                                                    per_band=self.per_band)
             model_output = model(x_in, self._scale_timesteps(t), **model_kwargs)
             mo = model_output.detach().float().permute(0, 2, 3, 4, 1).contiguous()
@@ -588,10 +622,14 @@ class GaussianDiffusion:
             terms = {"mse_wav": th.mean(mean_flat((x_start_dwt - model_output) ** 2), dim=0)}
             return terms, model_output, model_output_idwt
         # one kernel: 4 DWTs (LLL/3), the noise DWT (no /3, :1143-1145),
-        # q_sample, straight into the 32-channel model input (cwdm_prepare_batch)
-        x_in, x_start_dwt = ops.prepare_batch(target, x_start[keys[1]], x_start[keys[2]], x_start[keys[3]],
-                                              noise_img, self.q_coef_table(dev), t, self.num_timesteps,
-                                              per_band=self.per_band)
+        # q_sample, straight into the 32-channel model input (cwdm_prepare_batch);
+        # any other number of conditions: cwdm_prepare_batch_n, 8 + 8x channels
+        if brats:
+            x_in, x_start_dwt = ops.prepare_batch(target, *conds, noise_img, self.q_coef_table(dev), t,
+                                                  self.num_timesteps, per_band=self.per_band)
+        else:
+            x_in, x_start_dwt = ops.prepare_batch_n(target, conds, noise_img, self.q_coef_table(dev), t,
+                                                    self.num_timesteps, per_band=self.per_band)
         model_output = model(x_in, self._scale_timesteps(t), **model_kwargs)
         mo = model_output.float().contiguous()
         model_output_idwt = ops.idwt3d(mo.detach(), (V, 8 * V, 0, 1), B, 1, d, h, w, lll_mul3=True)

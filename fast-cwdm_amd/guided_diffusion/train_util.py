@@ -154,7 +154,9 @@ class TrainLoop:
             cond = {}
             d = dist_util.dev()
             if self.mode == "i2i":
-                batch = {k: (v.to(d) if th.is_tensor(v) else v) for k, v in batch.items()}
+                # the four BraTS keys, or the generic {"target": vol, "cond": [vol, ...]} (training_losses)
+                batch = {k: (v.to(d) if th.is_tensor(v) else
+                             [c.to(d) for c in v] if isinstance(v, (list, tuple)) else v) for k, v in batch.items()}
             else:
                 batch = batch.to(d)
             t0 = time.time()
@@ -266,7 +268,10 @@ class TrainLoop:
         plist = self.model.param_list() if hasattr(self.model, "param_list") else self.model.parameters()
         for p in plist:
             p.grad = None
-        batch_size = batch["t1n"].shape[0] if self.mode == "i2i" else batch.shape[0]
+        if self.mode == "i2i":
+            batch_size = (batch["target"] if "target" in batch else batch["t1n"]).shape[0]
+        else:
+            batch_size = batch.shape[0]
         t, weights = self.schedule_sampler.sample(batch_size, dist_util.dev())
         compute_losses = functools.partial(self.diffusion.training_losses, self.model, x_start=batch, t=t,
                                            model_kwargs=cond, labels=label, mode=self.mode, contr=self.contr)

@@ -213,6 +213,18 @@ int cwdm_prepare_batch(const float* target, const float* c1, const float* c2, co
                        const float* coef, int per_band, const int64_t* t, int64_t T, float* x_in, float* x0,
                        cwdm_stream_t stream);
 
+/* cwdm_prepare_batch_n: the same front end for 0 <= ncond <= 7 condition volumes
+ * (the reference's model family, 8 + 8x input channels: run.sh:65; x = 0 is the
+ * unconditional mode='default').  conds: HOST array of ncond device pointers
+ * (may be NULL when ncond = 0); they are passed on by value in the kernel
+ * arguments, no device table.  x_in (B, 8 + 8 ncond, d, h, w) = [x_t |
+ * DWT(conds[0]) | ... | DWT(conds[ncond - 1])], every condition's LLL / 3; x0 as
+ * above.  With ncond = 3 the outputs equal cwdm_prepare_batch's bit for bit.
+ * CWDM_E_UNSUPPORTED beyond 7 conditions. */
+int cwdm_prepare_batch_n(const float* target, const float* const* conds, int ncond, const float* eps_img,
+                         int64_t B, int64_t D, int64_t H, int64_t W, const float* coef, int per_band,
+                         const int64_t* t, int64_t T, float* x_in, float* x0, cwdm_stream_t stream);
+
 /* cwdm_prepare_batch2: the same front end for the 2-level block wavelet
  * representation (BASELINE config 5; no reference code -- the levels-1 front
  * end above with cwdm_wavelet2_analysis's transform, oracle/wavelet2.py):
@@ -768,6 +780,17 @@ int cwdm_adamw_device_step(float* p, const float* g, float* m, float* v, int64_t
  * out_layers.3, its mask regenerated by cwdm_dropout_bwd in the backward).
  * Topology and parameter names/shapes follow UNetModel.__init__
  * (unet.py:482-725) so reference state_dicts load unchanged.
+ *
+ * in_channels: any multiple of 8 (8 wavelet channels for the image plus 8 per
+ * condition volume), in every dtype.  Where it is no multiple of the dtype's K
+ * chunk (16 in bf16 / fp16: 8, 24, 40, ...) the plan copies x into a workspace
+ * tensor zero-padded to the chunk at the start of every forward (real zeros,
+ * written on every call) and input_blocks.0.0 runs on that copy with zero
+ * weight columns.  Nothing of this shows in the interface: x stays dense
+ * (B, D, H, W, in_channels), input_blocks.0.0.weight keeps the shape
+ * (model_channels, in_channels, 3, 3, 3), its gradient covers exactly those
+ * columns, and cwdm_unet_flops counts in_channels.  Plans with use_freq take a
+ * multiple of the chunk only (the wavelet pyramid reads x itself).
  * ------------------------------------------------------------------------- */
 typedef struct cwdm_unet cwdm_unet;
 typedef struct {

@@ -8,7 +8,7 @@ all-reduce overlapped when WORLD_SIZE > 1), fused AdamW over the flat
 parameters.  Prints one JSON line on rank 0 with steps/s (all ranks), the
 forward/backward conv TFLOP/s and the fraction of the dense bf16 MFMA peak.
 
-usage: python tools/train_bench.py [--grid 128] [--steps 5] [--dtype bf16] [--dropout P]
+usage: python tools/train_bench.py [--grid 128] [--steps 5] [--dtype bf16] [--dropout P] [--in-channels 8|16|..]
        python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/train_bench.py
 """
 import argparse
@@ -37,25 +37,34 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--dropout", type=float, default=0.0, help="UNetModel(dropout=P): the ResBlocks' in-kernel "
                     "Philox dropout (0 = the plan without it)")
+    ap.add_argument("--in-channels", type=int, default=32, help="8 + 8x: x condition volumes (32: the four BraTS "
+                    "modalities through cwdm_prepare_batch; 8: mode='default'; else the generic condition dict)")
     args = ap.parse_args()
     from guided_diffusion import dist_util, script_util, train_util
     os.environ.setdefault("CWDM_LOGDIR", os.path.join(ROOT, "gpurun_out", "train_bench"))
     dist_util.setup_dist()
     rank, world = dist.get_rank(), dist.get_world_size()
     dev = dist_util.dev()
-    margs = script_util.run_sh_model_args(diffusion_steps=1000, sample_schedule="direct", dropout=args.dropout)
+    cin = args.in_channels
+    mode = "default" if cin == 8 else "i2i"
+    margs = script_util.run_sh_model_args(diffusion_steps=1000, sample_schedule="direct", dropout=args.dropout,
+                                          in_channels=cin, mode=mode)
     keys = script_util.model_and_diffusion_defaults().keys()
     model, diffusion = script_util.create_model_and_diffusion(**{k: margs[k] for k in keys},
                                                               compute_dtype=args.dtype)
     seeded_weights(model, 1)
     model.to(dev)
     n2 = 2 * args.grid
-    batch = {k: torch.cat([phantom_gpu(n2, 100 * rank + 10 * i + j, dev) for i in range(args.batch)])
-             for j, k in enumerate(("t1n", "t1c", "t2w", "t2f"))}
+    vols = [torch.cat([phantom_gpu(n2, 100 * rank + 10 * i + j, dev) for i in range(args.batch)])
+            for j in range(cin // 8)]
+    if cin == 32:
+        batch = dict(zip(("t1n", "t1c", "t2w", "t2f"), vols))
+    else:
+        batch = vols[0] if cin == 8 else {"target": vols[0], "cond": vols[1:]}
     loop = train_util.TrainLoop(model=model, diffusion=diffusion, data=[batch], batch_size=args.batch,
-                                in_channels=32, image_size=n2, microbatch=-1, lr=1e-5, ema_rate="0.9999",
+                                in_channels=cin, image_size=n2, microbatch=-1, lr=1e-5, ema_rate="0.9999",
                                 log_interval=10 ** 9, contr="t1n", save_interval=10 ** 9, resume_checkpoint="",
-                                resume_step=0, mode="i2i", diffusion_steps=1000)
+                                resume_step=0, mode=mode, diffusion_steps=1000)
     for _ in range(args.warmup):
         loop.run_step(batch, {})
     torch.cuda.synchronize()
@@ -80,7 +89,7 @@ def main():
             "metric": "training steps/s (TrainLoop.run_step, i2i cWDM, 128^3 subbands)",
             "value": round(world * args.batch * args.steps / dt, 4), "unit": "volumes/s",
             "n_gpus": world, "steps": args.steps, "ms_per_step": round(per_step * 1e3, 2),
-            "dtype": args.dtype, "grid": g, "batch_per_gpu": args.batch, "dropout": args.dropout,
+            "dtype": args.dtype, "grid": g, "batch_per_gpu": args.batch, "dropout": args.dropout, "in_channels": cin,
             "conv_tflop_per_step": round((ffl + bfl) / 1e12, 2),
             "conv_tflops_achieved": round((ffl + bfl) / per_step / 1e12, 1),
             "mfma_frac": round((ffl + bfl) / per_step / 1e12 / peak, 4),
