@@ -1520,6 +1520,23 @@ extern "C" int cwdm_debug_v5_aa_timeout(int extra, int spin) {
   return CWDM_OK;
 }
 
+namespace cwdm {
+int dev_err_word(unsigned** word) {
+  static std::atomic<unsigned*> cached[64];   // per device: each has its own copy of the symbol
+  int dev = 0;
+  CWDM_HIP(hipGetDevice(&dev));
+  unsigned* p = dev < 64 ? cached[dev].load(std::memory_order_acquire) : nullptr;
+  if (!p) {
+    void* a = nullptr;
+    CWDM_HIP(hipGetSymbolAddress(&a, HIP_SYMBOL(g_cwdm_dev_err)));
+    p = static_cast<unsigned*>(a);
+    if (dev < 64) cached[dev].store(p, std::memory_order_release);
+  }
+  *word = p;
+  return CWDM_OK;
+}
+}  // namespace cwdm
+
 extern "C" int cwdm_device_status(int clear) {
   unsigned v = 0;
   CWDM_HIP(hipDeviceSynchronize());

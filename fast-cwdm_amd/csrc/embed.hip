@@ -11,11 +11,17 @@ namespace {
 
 __device__ __forceinline__ float silu_f(float v) { return v / (1.0f + expf(-v)); }
 
-// one workgroup per batch element
+// one workgroup per batch element.  label_w (null: no class conditioning) is label_emb.weight
+// [num_classes][E] and y int64[B]: the result is time_embed(t) + label_emb[y] (unet.py:763-774), one fp32
+// add on the fp32 result of the second Linear.  A label outside [0, num_classes) never indexes the table:
+// nothing is added for that sample and CWDM_DEV_E_LABEL is raised in the device error word (err).
 __global__ void __launch_bounds__(256) time_embed_kernel(const float* __restrict__ t, int mc,
                                                         const float* __restrict__ w1, const float* __restrict__ b1,
                                                         const float* __restrict__ w2, const float* __restrict__ b2,
-                                                        float* __restrict__ temb) {
+                                                        float* __restrict__ temb,
+                                                        const float* __restrict__ label_w,
+                                                        const long long* __restrict__ y, int num_classes,
+                                                        unsigned* __restrict__ err) {
   extern __shared__ float sm[];
   const int E = 4 * mc, half = mc / 2;
   float* sin_emb = sm;       // [mc]
@@ -38,11 +44,18 @@ __global__ void __launch_bounds__(256) time_embed_kernel(const float* __restrict
     hid[o] = silu_f(acc);
   }
   __syncthreads();
+  const float* lrow = nullptr;
+  if (label_w) {
+    const long long c = y[b];
+    if (c >= 0 && c < num_classes) lrow = label_w + c * E;
+    else if (threadIdx.x == 0)
+      __hip_atomic_fetch_or(err, (unsigned)CWDM_DEV_E_LABEL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   for (int o = threadIdx.x; o < E; o += blockDim.x) {
     float acc = b2[o];
     const float* wr = w2 + (long long)o * E;
     for (int i = 0; i < E; ++i) acc += wr[i] * hid[i];
-    temb[(long long)b * E + o] = acc;
+    temb[(long long)b * E + o] = lrow ? acc + lrow[o] : acc;
   }
 }
 
@@ -65,9 +78,16 @@ __global__ void __launch_bounds__(256) emb_proj_kernel(const float* __restrict__
 }  // namespace
 
 int launch_time_embed(const float* t, int B, int mc, const float* w1, const float* b1, const float* w2,
-                      const float* b2, float* temb, hipStream_t s) {
+                      const float* b2, float* temb, const float* label_w, const int64_t* y, int num_classes,
+                      hipStream_t s) {
   const size_t sm = (size_t)(mc + 4 * mc) * sizeof(float);
-  hipLaunchKernelGGL(time_embed_kernel, dim3(B), dim3(256), sm, s, t, mc, w1, b1, w2, b2, temb);
+  unsigned* err = nullptr;
+  if (label_w) {
+    CWDM_REQUIRE(y && num_classes > 0, CWDM_E_INVALID, "time_embed: a label table needs labels");
+    if (int rc = dev_err_word(&err)) return rc;
+  }
+  hipLaunchKernelGGL(time_embed_kernel, dim3(B), dim3(256), sm, s, t, mc, w1, b1, w2, b2, temb, label_w,
+                     reinterpret_cast<const long long*>(y), num_classes, err);
   CWDM_LAUNCHED();
   return CWDM_OK;
 }

@@ -679,6 +679,23 @@ __global__ void __launch_bounds__(256) temb_bwd_kernel(const float* __restrict__
   }
 }
 
+// label_emb.weight's gradient: one thread per (class c, column o) walks the batch in ascending order and adds
+// the rows whose label is c -- one writer per element, a fixed order, no atomics, no memset (a class absent
+// from the batch gets +0.0).  A label outside [0, num_classes) matches no c: its row goes nowhere, as the
+// forward added nothing for it.
+__global__ void __launch_bounds__(256) label_emb_bwd_kernel(const float* __restrict__ temb,
+                                                            const float* __restrict__ dsil,
+                                                            const long long* __restrict__ y, int B, int E,
+                                                            int num_classes, float* __restrict__ dlabel) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)num_classes * E) return;
+  const int c = (int)(i / E), o = (int)(i % E);
+  float s = 0.f;
+  for (int b = 0; b < B; ++b)
+    if (y[b] == c) s += __fmul_rn(dsil[(long long)b * E + o], dsilu_ref(temb[(long long)b * E + o]));
+  dlabel[i] = s;
+}
+
 template <typename F>
 int dispatch_mode(int mode, F&& f) {
   if (mode == 0) return f(std::integral_constant<int, 0>{});
@@ -721,6 +738,15 @@ int launch_temb_bwd(const float* t, int B, int mc, const float* w1, const float*
   CWDM_REQUIRE(sm <= 64 * 1024, CWDM_E_SHAPE, "time_embed backward: batch too large for one workgroup");
   hipLaunchKernelGGL(temb_bwd_kernel, dim3((unsigned)ceil_div(E, TEMB_R)), dim3(256), sm, s, t, B, mc, w1, b1, w2,
                      temb, dsil, dw1, db1, dw2, db2);
+  CWDM_LAUNCHED();
+  return CWDM_OK;
+}
+
+int launch_label_emb_bwd(const float* temb, const float* dsil, const int64_t* y, int B, int E, int num_classes,
+                         float* dlabel, hipStream_t s) {
+  const long long n = (long long)num_classes * E;
+  hipLaunchKernelGGL(label_emb_bwd_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, temb, dsil,
+                     reinterpret_cast<const long long*>(y), B, E, num_classes, dlabel);
   CWDM_LAUNCHED();
   return CWDM_OK;
 }

@@ -152,9 +152,13 @@ unsigned* plan_aa_counters(unsigned* sync);
 // layout.hip: dst (voxels, c_dst) = [src (voxels, c_src) | zeros], channels-last, both 16-byte aligned with whole
 // 16-byte quads of channels; every lane of dst is written on every call
 int pad_channels(const void* src, int c_src, void* dst, int c_dst, int dtype, int64_t voxels, hipStream_t s);
-// embed.hip
+// conv3d_v5.hip: the device address of the sticky error word behind cwdm_device_status (looked up once;
+// call it outside stream capture first: cwdm_unet_set_labels does)
+int dev_err_word(unsigned** word);
+// embed.hip (label_w null: no class conditioning; else temb += label_w[y[b]], y int64[B] on the device)
 int launch_time_embed(const float* t, int B, int mc, const float* w1, const float* b1, const float* w2,
-                      const float* b2, float* temb, hipStream_t s);
+                      const float* b2, float* temb, const float* label_w, const int64_t* y, int num_classes,
+                      hipStream_t s);
 int launch_emb_proj(const float* temb, int B, int E, const float* W, const float* bias, int R, float* out,
                     hipStream_t s);
 // grad.hip
@@ -163,6 +167,10 @@ int launch_emb_bwd(const float* dEb, int R, int n, int B, const float* temb, int
 int launch_temb_bwd(const float* t, int B, int mc, const float* w1, const float* b1, const float* w2,
                     const float* temb, const float* dsil, float* dw1, float* db1, float* dw2, float* db2,
                     hipStream_t s);
+// d label_emb.weight[c][:] = sum over b with y[b] == c, b ascending, of dsil[b][:] * SiLU'(temb[b][:]) (the
+// gradient of temb launch_temb_bwd consumes); every row written, absent classes as +0.0
+int launch_label_emb_bwd(const float* temb, const float* dsil, const int64_t* y, int B, int E, int num_classes,
+                         float* dlabel, hipStream_t s);
 // a FiLM block's out_layers.0 in gn_silu_bwd_impl: beta (d s needs it), the rows [s | t] and where d s, d t go
 // (batch strides in floats), and chs_c (optional): the per-channel sums of the written dx0 over voxels and
 // batch entries, added to chs_c[c] in a fixed order -- the bias gradient of the block's conv1

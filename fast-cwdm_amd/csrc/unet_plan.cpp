@@ -184,6 +184,8 @@ struct cwdm_unet {
   std::vector<AttnStep> attns;
   std::vector<DropStep> drops;
   uint64_t dropout_seed = 0;      // cwdm_unet_set_dropout_seed: read when a dropout step or its backward is launched
+  const int64_t* labels = nullptr;  // cwdm_unet_set_labels: device int64[B], read when the time embedding or the
+                                    // table's gradient is launched (class-conditional plans)
   std::vector<Step> steps;
   struct Alias { std::string name; int owner, before; };
   std::vector<Alias> aliases;     // WavUNetModel: second state_dict name of a reused parameter; before = the
@@ -198,6 +200,7 @@ struct cwdm_unet {
                                                          // (-1: the conv bias is not folded, WavUNet up/down)
   std::vector<int> emb_rows_off, emb_rows_n;
   int te_w1, te_b1, te_w2, te_b2;
+  int label_w = -1;               // label_emb.weight (num_classes > 0)
   std::vector<Block> blocks;
   int head_g = -1, head_c = -1, head_p_begin = 0;
   std::vector<int64_t> goff;      // flat gradient offset (elements) per parameter
@@ -206,6 +209,7 @@ struct cwdm_unet {
   int64_t packed_bwd_bytes = 0;
   std::vector<char> ginit;        // backward: gradient buffer of tensor written yet
   int64_t off_te_w1, off_te_b1, off_te_w2, off_te_b2, off_emb_w, off_emb_b;
+  int64_t off_label = -1;         // the fp32 table as it stands
   int64_t packed_bytes = 0;
   int64_t split3_tmp = -1;      // fp32 staging of head_split3_pack (one region, the packs run in stream order)
   // profiling
@@ -233,6 +237,8 @@ void build(cwdm_unet* u) {
   u->te_b1 = u->add_param("time_embed.0.bias", {E});
   u->te_w2 = u->add_param("time_embed.2.weight", {E, E});
   u->te_b2 = u->add_param("time_embed.2.bias", {E});
+  // the reference registers label_emb between time_embed and input_blocks (unet.py:541-542)
+  if (c.num_classes > 0) u->label_w = u->add_param("label_emb.weight", {c.num_classes, E});
 
   auto new_tensor = [&](int level, int ch) {
     u->tensors.push_back({level, ch});
@@ -670,6 +676,7 @@ void build(cwdm_unet* u) {
   u->off_te_b1 = take(u->params[u->te_b1].numel() * 4);
   u->off_te_w2 = take(u->params[u->te_w2].numel() * 4);
   u->off_te_b2 = take(u->params[u->te_b2].numel() * 4);
+  if (u->label_w >= 0) u->off_label = take(u->params[u->label_w].numel() * 4);
   u->off_emb_w = take((int64_t)u->R * E * 4);
   u->off_emb_b = take((int64_t)u->R * 4);
   int64_t split3_max = 0;
@@ -1064,6 +1071,9 @@ extern "C" int cwdm_unet_create(const cwdm_unet_config* cfg, cwdm_unet** plan) {
                "cwdm_unet_create: dropout must lie in [0, 1)");
   CWDM_REQUIRE(!(cfg->dropout > 0.0 && cfg->use_freq), CWDM_E_UNSUPPORTED,
                "cwdm_unet_create: dropout with use_freq (WavUNetModel's ResBlocks are not covered)");
+  CWDM_REQUIRE(cfg->num_classes >= 0, CWDM_E_INVALID, "cwdm_unet_create: num_classes must not be negative");
+  CWDM_REQUIRE(!(cfg->num_classes > 0 && cfg->use_freq), CWDM_E_UNSUPPORTED,
+               "cwdm_unet_create: num_classes with use_freq (WavUNetModel's class conditioning is not covered)");
   if (cfg->bottleneck_attention) {
     CWDM_REQUIRE(!cfg->use_freq, CWDM_E_UNSUPPORTED,
                  "cwdm_unet_create: bottleneck_attention with use_freq (WavUNetModel's middle block is not covered)");
@@ -1117,6 +1127,18 @@ extern "C" void cwdm_unet_destroy(cwdm_unet* u) {
 extern "C" int cwdm_unet_set_dropout_seed(cwdm_unet* u, uint64_t seed) {
   CWDM_REQUIRE(u, CWDM_E_INVALID, "cwdm_unet_set_dropout_seed: null plan");
   u->dropout_seed = seed;
+  return CWDM_OK;
+}
+
+extern "C" int cwdm_unet_set_labels(cwdm_unet* u, const int64_t* y_dev) {
+  CWDM_REQUIRE(u, CWDM_E_INVALID, "cwdm_unet_set_labels: null plan");
+  CWDM_REQUIRE(u->cfg.num_classes > 0, CWDM_E_INVALID,
+               "cwdm_unet_set_labels: the plan has no classes (num_classes = 0)");
+  CWDM_REQUIRE(y_dev, CWDM_E_INVALID, "cwdm_unet_set_labels: null labels");
+  // (the error word's address is looked up here, never inside a stream capture)
+  unsigned* err = nullptr;
+  if (int rc = cwdm::dev_err_word(&err)) return rc;
+  u->labels = y_dev;
   return CWDM_OK;
 }
 
@@ -1197,6 +1219,7 @@ extern "C" int cwdm_unet_pack(const cwdm_unet* uc, const float* const* P, void* 
   cp(u->te_b1, u->off_te_b1);
   cp(u->te_w2, u->off_te_w2);
   cp(u->te_b2, u->off_te_b2);
+  if (u->label_w >= 0) cp(u->label_w, u->off_label);
   float* ew = reinterpret_cast<float*>(base + u->off_emb_w);
   float* eb = reinterpret_cast<float*>(base + u->off_emb_b);
   for (size_t k = 0; k < u->emb_rows_w.size(); ++k) {
@@ -1331,7 +1354,8 @@ struct Forward : PlanView {
   int begin() {
     CWDM_HIP(hipMemsetAsync(sync, 0, cwdm::plan_sync_bytes(), s));
     if (int rc = launch_time_embed(t, (int)B, u->cfg.model_channels, P(u->off_te_w1), P(u->off_te_b1), P(u->off_te_w2),
-                                   P(u->off_te_b2), temb, s))
+                                   P(u->off_te_b2), temb, u->label_w >= 0 ? P(u->off_label) : nullptr, u->labels,
+                                   u->cfg.num_classes, s))
       return rc;
     if (int rc = launch_emb_proj(temb, (int)B, u->E, P(u->off_emb_w), P(u->off_emb_b), u->R, ebias, s)) return rc;
     return u->profiling ? prof_begin() : CWDM_OK;
@@ -1615,6 +1639,8 @@ static int unet_forward_impl(cwdm_unet* u, const void* packed, const void* x, co
                              cwdm_stream_t stream, const cwdm_sampler_args* samp, int* fused) {
   CWDM_REQUIRE(u && packed && x && t && out && ws, CWDM_E_INVALID, "cwdm_unet_forward: null pointer");
   CWDM_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, CWDM_E_SHAPE, "cwdm_unet_forward: empty grid");
+  CWDM_REQUIRE(u->cfg.num_classes == 0 || u->labels, CWDM_E_INVALID,
+               "cwdm_unet_forward: a class-conditional plan needs its labels (cwdm_unet_set_labels)");
   const int64_t div = int64_t(1) << (u->cfg.num_levels - (u->cfg.use_freq ? 0 : 1));
   CWDM_REQUIRE(D % div == 0 && H % div == 0 && W % div == 0, CWDM_E_SHAPE,
                "cwdm_unet_forward: every subband edge must be divisible by " + std::to_string(div));
@@ -2344,8 +2370,12 @@ struct Backward : PlanView {
     int rc;
     if ((rc = bias_grad(grd(c0.out), 0, c0.cout, GR(c0.b_p)))) return rc;
     if ((rc = stem_wgrad())) return rc;
-    return launch_temb_bwd(t, (int)B, u->cfg.model_channels, P(u->off_te_w1), P(u->off_te_b1), P(u->off_te_w2), temb,
-                           dsil, GR(u->te_w1), GR(u->te_b1), GR(u->te_w2), GR(u->te_b2), s);
+    if ((rc = launch_temb_bwd(t, (int)B, u->cfg.model_channels, P(u->off_te_w1), P(u->off_te_b1), P(u->off_te_w2), temb,
+                              dsil, GR(u->te_w1), GR(u->te_b1), GR(u->te_w2), GR(u->te_b2), s)))
+      return rc;
+    // class conditioning: emb = time_embed(t) + label_emb[y], so the table's rows collect the same gradient
+    if (u->label_w < 0) return CWDM_OK;
+    return launch_label_emb_bwd(temb, dsil, u->labels, (int)B, u->E, u->cfg.num_classes, GR(u->label_w), s);
   }
 };
 
@@ -2361,6 +2391,8 @@ extern "C" int cwdm_unet_backward(cwdm_unet* u, const void* packed, const void* 
   CWDM_REQUIRE(0 <= seg_begin && seg_begin <= seg_end && seg_end <= nseg, CWDM_E_INVALID,
                "cwdm_unet_backward: bad segment range");
   CWDM_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, CWDM_E_SHAPE, "cwdm_unet_backward: empty grid");
+  CWDM_REQUIRE(u->cfg.num_classes == 0 || u->labels, CWDM_E_INVALID,
+               "cwdm_unet_backward: a class-conditional plan needs its labels (cwdm_unet_set_labels)");
   const int64_t div = int64_t(1) << (u->cfg.num_levels - (u->cfg.use_freq ? 0 : 1));
   CWDM_REQUIRE(D % div == 0 && H % div == 0 && W % div == 0, CWDM_E_SHAPE,
                "cwdm_unet_backward: every subband edge must be divisible by " + std::to_string(div));

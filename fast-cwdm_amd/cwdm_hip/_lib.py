@@ -15,6 +15,8 @@ CWDM_BF16 = 1
 CWDM_F64 = 2
 CWDM_F16 = 3
 
+DEV_E_AA_TIMEOUT, DEV_E_LABEL = 1, 2   # cwdm_device_status bits
+
 E_INVALID, E_SHAPE, E_HIP, E_WORKSPACE, E_INDEX, E_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 
 i64 = ctypes.c_int64
@@ -98,6 +100,7 @@ class UNetConfig(ctypes.Structure):
         ("num_head_channels", ctypes.c_int), ("attn_new_order", ctypes.c_int),
         ("use_scale_shift_norm", ctypes.c_int),
         ("dropout", ctypes.c_double),
+        ("num_classes", ctypes.c_int),
     ]
 
 
@@ -239,6 +242,7 @@ _PROTOS = {
                                          ctypes.c_double, ctypes.c_double, i64, vp, vp]),
     "cwdm_unet_create": (ctypes.c_int, [ctypes.POINTER(UNetConfig), ctypes.POINTER(vp)]),
     "cwdm_unet_set_dropout_seed": (ctypes.c_int, [vp, ctypes.c_uint64]),
+    "cwdm_unet_set_labels": (ctypes.c_int, [vp, vp]),
     "cwdm_unet_destroy": (None, [vp]),
     "cwdm_unet_num_params": (ctypes.c_int, [vp]),
     "cwdm_unet_num_aliases": (ctypes.c_int, [vp]),

@@ -35,7 +35,8 @@ def check_device_status(where):
         check(st, where)
     if st:
         raise RuntimeError(f"{where}: device error word {st:#x} (CWDM_DEV_E_AA_TIMEOUT = 1: a persistent conv's "
-                           f"workgroups were not all resident; results of this call are invalid)")
+                           f"workgroups were not all resident; CWDM_DEV_E_LABEL = 2: a class label outside "
+                           f"[0, num_classes), nothing was added for that sample; results of this call are invalid)")
 
 
 def _p(t):

@@ -32,7 +32,7 @@ class UNetPlan:
     def __init__(self, in_channels, model_channels, out_channels, num_res_blocks, channel_mult, num_groups,
                  dtype="fp32", resblock_updown=True, use_freq=False, additive_skips=False,
                  bottleneck_attention=False, num_heads=1, num_head_channels=-1, use_new_attention_order=False,
-                 use_scale_shift_norm=False, dropout=0.0):
+                 use_scale_shift_norm=False, dropout=0.0, num_classes=0):
         cfg = _lib.UNetConfig()
         cfg.in_channels, cfg.model_channels, cfg.out_channels = in_channels, model_channels, out_channels
         cfg.num_res_blocks, cfg.num_levels = num_res_blocks, len(channel_mult)
@@ -54,6 +54,10 @@ class UNetPlan:
         # > 0: a training plan whose every forward drops (cwdm_unet_config.dropout); set_dropout_seed names the masks
         cfg.dropout = float(dropout)
         self.dropout = float(dropout)
+        # > 0: label_emb.weight after time_embed.2.bias, emb = time_embed(t) + label_emb[y]; set_labels names y
+        cfg.num_classes = int(num_classes)
+        self.num_classes = int(num_classes)
+        self._labels = None
         self.use_freq = bool(use_freq)
         self.dtype = cfg.dtype
         self.torch_dtype = TORCH_DT[cfg.dtype]
@@ -115,6 +119,16 @@ class UNetPlan:
         """The 64-bit seed the plan's dropout masks are drawn with (host state, read at launch): set before a
         forward and again before its backward."""
         check(lib().cwdm_unet_set_dropout_seed(self._h, int(seed)))
+
+    def set_labels(self, y):
+        """The labels of a class-conditional plan: ``y`` a contiguous int64 device tensor (B,), read at launch
+        (host state of the plan, like the dropout seed): set before a forward and again before its backward.
+        The plan keeps a reference; a captured graph bakes the pointer in, so change ``y`` in place only."""
+        _need_cuda(y)
+        if y.dtype != torch.int64 or y.dim() != 1 or not y.is_contiguous():
+            raise ValueError("set_labels: a contiguous int64 tensor of shape (B,) expected")
+        check(lib().cwdm_unet_set_labels(self._h, ctypes.c_void_p(y.data_ptr())), "set_labels")
+        self._labels = y
 
     def workspace_bytes(self, B, D, H, W):
         n = int(lib().cwdm_unet_workspace_bytes(self._h, B, D, H, W))

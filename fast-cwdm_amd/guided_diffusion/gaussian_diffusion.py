@@ -369,10 +369,15 @@ class GaussianDiffusion:
             except ImportError:  # pragma: no cover
                 pass
         unet = _native_unet(model)
-        if unet is not None and denoised_fn is None and cond_fn is None and not model_kwargs:
+        # the native loop takes no model_kwargs, or exactly the labels of a class-conditional native model
+        y = None
+        if unet is not None and model_kwargs and set(model_kwargs) == {"y"} and \
+                getattr(unet, "num_classes", None) is not None and th.is_tensor(model_kwargs["y"]):
+            y = model_kwargs["y"]
+        if unet is not None and denoised_fn is None and cond_fn is None and (not model_kwargs or y is not None):
             steps = self._native_loop(unet, img, indices, cond, clip_denoised, noise_fn,
                                       fresh_outputs=not reuse_outputs, need_pred=not reuse_outputs,
-                                      update=update, eta=eta)
+                                      update=update, eta=eta, y=y)
         else:
             steps = self._generic_loop(model, img, indices, shape[0], device, clip_denoised, denoised_fn,
                                        cond_fn, model_kwargs, cond, noise_fn, update, eta)
@@ -400,8 +405,12 @@ class GaussianDiffusion:
                 img = out["sample"]
 
     def _native_loop(self, unet, img, indices, cond, clip_denoised, noise_fn=None, graph=None, fresh_outputs=True,
-                     need_pred=True, update=0, eta=0.0):
+                     need_pred=True, update=0, eta=0.0, y=None):
         """Channels-last resident loop for the native UNetModel.
+
+        y: the labels of a class-conditional model, set on the plan once, before
+        the first step and before capture; the device copy lives as long as the
+        loop (a captured graph reads it through the pointer it baked in).
 
         graph: capture one denoising step (U-Net launch list + fused sampler
         epilogue) in a HIP graph and replay it for every later step (default:
@@ -446,6 +455,11 @@ class GaussianDiffusion:
         t = th.empty((B,), dtype=th.int64, device=dev)
         t_model = th.empty((B,), dtype=th.float32, device=dev)
         ddim = update == 1
+        if (y is not None) != (getattr(unet, "num_classes", None) is not None):
+            raise AssertionError("must specify y if and only if the model is class-conditional")
+        if y is not None:
+            y = unet._labels(y, B, dev)   # held by this generator's frame (and by the plan) until the loop ends
+            plan.set_labels(y)
 
         philox = noise_fn is None and self.native_noise == "philox"
         seed = int(th.randint(0, 2 ** 62, (1,)).item()) if (philox and not ddim) else None

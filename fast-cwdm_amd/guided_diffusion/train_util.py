@@ -153,11 +153,18 @@ class TrainLoop:
             batch = self._next_batch()
             cond = {}
             d = dist_util.dev()
+            # a class-conditional model's labels (an extension, like {"target", "cond"}): a batch dict's "y" key,
+            # int (B,), becomes the step's model_kwargs; mode='default' then takes {"target": vol, "y": y}
             if self.mode == "i2i":
                 # the four BraTS keys, or the generic {"target": vol, "cond": [vol, ...]} (training_losses)
                 batch = {k: (v.to(d) if th.is_tensor(v) else
                              [c.to(d) for c in v] if isinstance(v, (list, tuple)) else v) for k, v in batch.items()}
+                if "y" in batch:
+                    cond["y"] = batch.pop("y")
             else:
+                if isinstance(batch, dict) and "y" in batch:
+                    cond["y"] = batch["y"].to(d)
+                    batch = batch["target"]
                 batch = batch.to(d)
             t0 = time.time()
             lossmse, sample, sample_idwt = self.run_step(batch, cond)

@@ -28,6 +28,16 @@ softmax(QK^T)V and proj_out + residual, three launches.
 ``attention_resolutions`` must stay empty.  Anything else raises
 NotImplementedError.
 
+``num_classes=n`` builds the reference's class-conditional model: one more
+parameter, ``label_emb.weight`` (n, 4 model_channels), right after
+``time_embed.2.bias`` (the reference's state_dict order), and ``forward(x,
+timesteps, y)`` computes ``emb = time_embed(t) + label_emb(y)`` inside the
+time-embedding kernel (no launch added; the backward adds one deterministic
+reduction for the table).  ``y`` is an integer tensor of shape
+(B,); a host tensor is range-checked on the host (IndexError), a device tensor
+is not read back: a label outside [0, n) adds nothing for its sample and raises
+CWDM_DEV_E_LABEL in the device error word (``ops.check_device_status``).
+
 ``dropout=p`` (0 <= p < 1, else ValueError) is the reference's nn.Dropout(p)
 between every ResBlock's out_layers SiLU and its conv, and nowhere else; no
 parameters, so state_dicts are those of p = 0.  It is active iff
@@ -106,8 +116,8 @@ class UNetModel(nn.Module):
             unsupported.append("resblock_updown=False with conv_resample=False (parameter-free pool / nearest layers)")
         if resample_2d:
             unsupported.append("resample_2d=True")
-        if num_classes is not None:
-            unsupported.append("class conditioning")
+        if num_classes is not None and num_classes < 1:
+            raise ValueError(f"num_classes must be None or positive, got {num_classes!r}")
         if unsupported:
             raise NotImplementedError("fast-cwdm_amd UNetModel covers the run.sh configuration only; unsupported: "
                                       + ", ".join(unsupported))
@@ -247,7 +257,9 @@ class UNetModel(nn.Module):
         block's proj_out (:340)."""
         with th.no_grad():
             for name, p in self.named_parameters():
-                if name.endswith("out_layers.3.weight") or name.endswith("out_layers.3.bias") or \
+                if name == "label_emb.weight":
+                    p.normal_()   # nn.Embedding's default, N(0, 1)
+                elif name.endswith("out_layers.3.weight") or name.endswith("out_layers.3.bias") or \
                         name.startswith("out.2.") or name.startswith("middle_block.1.proj_out."):
                     p.zero_()
                 elif p.dim() == 1 and (".in_layers.0." in name or ".out_layers.0." in name or
@@ -277,7 +289,8 @@ class UNetModel(nn.Module):
                                         num_heads=self.num_heads, num_head_channels=self.num_head_channels,
                                         use_new_attention_order=self.use_new_attention_order,
                                         use_scale_shift_norm=self.use_scale_shift_norm,
-                                        dropout=self.dropout if drop else 0.0)
+                                        dropout=self.dropout if drop else 0.0,
+                                        num_classes=self.num_classes or 0)
         return self._plans[key]
 
     def _drops(self):
@@ -376,22 +389,39 @@ class UNetModel(nn.Module):
         return self
 
     # ---- forward ------------------------------------------------------------
-    def forward_ndhwc(self, x_ndhwc, t_f32, out_ndhwc):
+    def _labels(self, y, B, device):
+        """``y`` as the plan reads it: contiguous int64 (B,) on ``device``.  A host tensor is range-checked
+        here for free; a device tensor is not read back (the kernel refuses to index with a bad label and
+        flags it in the device error word)."""
+        assert y.shape == (B,), f"y must have shape ({B},), got {tuple(y.shape)}"
+        if not y.is_cuda and B:
+            ymin, ymax = int(y.min()), int(y.max())
+            if ymin < 0 or ymax >= self.num_classes:
+                raise IndexError(f"Labels out of bounds: min={ymin}, max={ymax}, num_classes={self.num_classes}")
+        return y.detach().to(device=device, dtype=th.int64).contiguous()
+
+    def forward_ndhwc(self, x_ndhwc, t_f32, out_ndhwc, y=None):
         """Fast seam: x (B, D, H, W, in) in the compute dtype, t fp32[B] (model
         timesteps), out (B, D, H, W, out) fp32; all device tensors.  A sampling
         seam: it never drops, whatever ``dropout`` and the training flag are (only
-        ``forward``, the nn.Module call, applies dropout)."""
+        ``forward``, the nn.Module call, applies dropout).  ``y`` (class-conditional
+        models): the labels of this and every later call, until others are set."""
         B, D, H, W, C = x_ndhwc.shape
         assert C == self.in_channels
+        if y is not None:
+            self.plan.set_labels(self._labels(y, B, x_ndhwc.device))
         return self.plan.forward(self.packed_weights(), x_ndhwc, t_f32, out_ndhwc, B, D, H, W)
 
-    def forward_step_ndhwc(self, x_ndhwc, t_f32, step):
+    def forward_step_ndhwc(self, x_ndhwc, t_f32, step, y=None):
         """forward_ndhwc followed by the sampling step ``step`` (ops.sampler_args,
         model_out = the (B, D, H, W, out) fp32 buffer), fused into the output
         head when it qualifies; returns whether it was fused.  Never drops (see
-        forward_ndhwc): the native p_sample_loop and the graph loop run through here."""
+        forward_ndhwc): the native p_sample_loop and the graph loop run through here,
+        which set ``y`` once, before the first step and before capture."""
         B, D, H, W, C = x_ndhwc.shape
         assert C == self.in_channels
+        if y is not None:
+            self.plan.set_labels(self._labels(y, B, x_ndhwc.device))
         return self.plan.forward_step(self.packed_weights(), x_ndhwc, t_f32, step, B, D, H, W)
 
     def forward(self, x, timesteps, y=None):
@@ -402,6 +432,8 @@ class UNetModel(nn.Module):
             assert x.device == self.devices[0], f"{x.device=} does not match {self.devices[0]=}"
         B, C, D, H, W = x.shape
         assert C == self.in_channels
+        if y is not None:
+            y = self._labels(y, B, x.device)
         params = self.param_list()
         if th.is_grad_enabled() and any(p.requires_grad for p in params):
             if self.direct_grads and _ANCHOR_ON and all(p.grad is None for p in params):
@@ -412,17 +444,19 @@ class UNetModel(nn.Module):
                 anchor = self.__dict__.get("_grad_anchor")
                 if anchor is None:
                     anchor = self._grad_anchor = th.zeros((), requires_grad=True)
-                return _UNetTrain.apply(self, x, timesteps, anchor)
-            return _UNetTrain.apply(self, x, timesteps, *params)
+                return _UNetTrain.apply(self, x, timesteps, y, anchor)
+            return _UNetTrain.apply(self, x, timesteps, y, *params)
         xin, t = self._prep_inputs(x, timesteps)
         out_nd = th.empty((B, D, H, W, self.out_channels), dtype=th.float32, device=x.device)
         if self._drops():
             # train() under no_grad drops too, as nn.Dropout does
             plan = self._plan(self.compute_dtype, drop=True)
             plan.set_dropout_seed(self._draw_dropout_seed())
+            if y is not None:
+                plan.set_labels(y)
             plan.forward(self.packed_weights(), xin, t, out_nd, B, D, H, W)
         else:
-            self.forward_ndhwc(xin, t, out_nd)
+            self.forward_ndhwc(xin, t, out_nd, y)
         return self._to_ncdhw(out_nd)
 
     def _prep_inputs(self, x, timesteps):
@@ -452,7 +486,7 @@ class _UNetTrain(th.autograd.Function):
     ranges while later segments compute."""
 
     @staticmethod
-    def forward(ctx, model, x, timesteps, *params):
+    def forward(ctx, model, x, timesteps, y, *params):
         ctx.anchored = len(params) == 1 and params[0] is model.__dict__.get("_grad_anchor")
         B, C, D, H, W = x.shape
         # dropout: the training plan, and this call's seed, handed to the plan before the forward and again
@@ -463,6 +497,10 @@ class _UNetTrain(th.autograd.Function):
         ctx.drop_seed = model._draw_dropout_seed() if drop else None
         if drop:
             plan.set_dropout_seed(ctx.drop_seed)
+        # the labels travel like the seed: set before the forward and again before each backward segment
+        ctx.labels = y
+        if y is not None:
+            plan.set_labels(y)
         xin, t = model._prep_inputs(x, timesteps)
         # the training workspace: the forward keeps each DMA-staged conv's
         # activated input there for the backward's weight gradients
@@ -494,11 +532,15 @@ class _UNetTrain(th.autograd.Function):
         if hook is None:
             if ctx.drop_seed is not None:
                 plan.set_dropout_seed(ctx.drop_seed)
+            if ctx.labels is not None:
+                plan.set_labels(ctx.labels)
             plan.backward(packed, packed_bwd, xin, t, dout, grads, B, D, H, W, ws, gws, 0, nseg)
         else:
             for seg in range(nseg):
                 if ctx.drop_seed is not None:
                     plan.set_dropout_seed(ctx.drop_seed)
+                if ctx.labels is not None:
+                    plan.set_labels(ctx.labels)
                 plan.backward(packed, packed_bwd, xin, t, dout, grads, B, D, H, W, ws, gws, seg, seg + 1)
                 off, n = plan.segment_range(seg)
                 hook(seg, grads, off, n)
@@ -526,5 +568,5 @@ class _UNetTrain(th.autograd.Function):
             else:
                 out.append(view)
         if ctx.anchored:
-            return (None, None, None, None)
-        return (None, None, None, *out)
+            return (None, None, None, None, None)
+        return (None, None, None, None, *out)

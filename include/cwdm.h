@@ -564,7 +564,11 @@ int cwdm_debug_v5_aa_timeout(int extra, int spin);
  * held by another process or masked; the conv's output is then not valid).
  * Synchronises the device; clear != 0 resets the word.  Returns the bits, or a
  * negative CWDM_E_* code. */
-enum { CWDM_DEV_E_AA_TIMEOUT = 1 };
+enum {
+  CWDM_DEV_E_AA_TIMEOUT = 1,
+  CWDM_DEV_E_LABEL = 2   /* a class-conditional U-Net forward met a label outside [0, num_classes): the table
+                            was not indexed and nothing was added for that sample (cwdm_unet_set_labels) */
+};
 int cwdm_device_status(int clear);
 
 /* Diagnostics / tests only: the fused GroupNorm finalize + pre-pass the plan
@@ -777,7 +781,8 @@ int cwdm_adamw_device_step(float* p, const float* g, float* m, float* v, int64_t
  * FiLM after out_layers.0: cwdm_gn_finalize_film folds it into the norm's
  * scale / shift table, no launch added; with dropout > 0, a training plan:
  * one cwdm_gn_silu_dropout pass per ResBlock between out_layers.0 and
- * out_layers.3, its mask regenerated by cwdm_dropout_bwd in the backward).
+ * out_layers.3, its mask regenerated by cwdm_dropout_bwd in the backward;
+ * with num_classes > 0, label_emb[y] added to the time embedding).
  * Topology and parameter names/shapes follow UNetModel.__init__
  * (unet.py:482-725) so reference state_dicts load unchanged.
  *
@@ -827,6 +832,12 @@ typedef struct {
                                seed = cwdm_unet_set_dropout_seed); the backward masks that conv's input gradient
                                with cwdm_dropout_bwd.  Same parameters and packed layouts as with 0.  Not with
                                use_freq.  0.0 (and a zeroed struct): off, the plan is unchanged */
+  int num_classes;          /* > 0: class conditioning (unet.py:541-542, :763-774): one more parameter,
+                               label_emb.weight (num_classes, 4 model_channels), fp32, right after
+                               time_embed.2.bias; every forward computes emb = time_embed(t) + label_emb[y]
+                               inside the time-embedding kernel (no launch added), y = cwdm_unet_set_labels;
+                               the backward adds one launch (the table's gradient, last segment).  Not with
+                               use_freq; < 0 is refused.  0 (and a zeroed struct): none, the plan is unchanged */
 } cwdm_unet_config;
 
 int cwdm_unet_create(const cwdm_unet_config* cfg, cwdm_unet** plan);
@@ -834,6 +845,14 @@ int cwdm_unet_create(const cwdm_unet_config* cfg, cwdm_unet** plan);
  * launches (not captured on the stream).  Set it before a forward and again, to the same value, before that
  * forward's backward: forwards and backwards of several calls may then interleave. */
 int cwdm_unet_set_dropout_seed(cwdm_unet* plan, uint64_t seed);
+/* The labels of a class-conditional plan (num_classes > 0): y_dev = device int64[B], one class per sample.
+ * Like the dropout seed the pointer is host state of the plan, read whenever a forward or a backward
+ * launches; set it before a forward and again before that forward's backward.  A captured graph bakes the
+ * pointer in: the caller keeps the tensor alive and changes it in place only.  A forward or backward of a
+ * class-conditional plan without labels, and labels on a plan without classes, return CWDM_E_INVALID.
+ * y[b] outside [0, num_classes) never indexes the table: the forward adds nothing for that sample, the
+ * backward gives its row to no class, and CWDM_DEV_E_LABEL is set in the device error word. */
+int cwdm_unet_set_labels(cwdm_unet* plan, const int64_t* y_dev);
 void cwdm_unet_destroy(cwdm_unet* plan);
 int cwdm_unet_num_params(const cwdm_unet* plan);
 int cwdm_unet_param_info(const cwdm_unet* plan, int i, char* name, int name_cap,
